@@ -15,8 +15,16 @@ scaling + ||K|| estimate; PDHG kernel: the iterations), plus the result all-gath
 Default schedule "seeded" (dervet_hip/sweep.py): the windows of 1 in 32 scenarios (battery-energy order) are
 solved from zero first, then every other window warm from its nearest seed's solution of the same month --
 two solver calls per step, every window solved once per step to the same KKT tolerance; nothing carries over
-between steps (the seed phase starts from zero and the warm phase overwrites every warm start).  After the
-timed steps the same batch is solved once more with every window cold, reported as schedule.cold_*.
+between steps (the seed phase starts from zero and the warm phase overwrites every warm start).
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does what the headline figure needs and no more: it builds the
+batch, warms up, times the N steps, writes the last step's outputs when `--dump-outputs DIR` is given (stats / istats of
+every window, x / y of a fixed seeded sample of windows, as DIR/<name>.npy; the inputs are seeded, so two builds of
+the library can be compared output for output) and prints the JSON line.  Everything else runs only with `--full`:
+the all-cold reference solve, the CPU baselines with the HiGHS parity check, and the measured HBM copy ceiling of the
+roofline object; their fields are null on a plain line.
+
+`--full`: after the timed steps the same batch is solved once more with every window cold, reported as schedule.cold_*.
 The CPU baseline (rank 0, N=1 only) times two CPU solvers on bounded samples of the same windows, on the box's
 16-core CPU share: the same restarted-Halpern PDHG in C++/OpenMP behind the same C ABI (oracle/cpu_pdhg.cpp, every
 window cold -- compare with schedule.cold_windows_per_s), which is the faster of the two and gives `value`, and
@@ -100,6 +108,47 @@ def outputs_sha(dev):
     return h.hexdigest()
 
 
+DUMP_SEED = 20250217          # the sample of windows whose x / y are dumped (fixed: the same windows in every run)
+DUMP_SAMPLE_BYTES = 24 << 20  # x + y of the sampled windows: with their gathered rows (N > 1; fewer bytes than x) and
+#                               the stats / istats of the default batch's every window (5.8 MB), under 64 MB in all
+
+
+def dump_sample(desc, budget=DUMP_SAMPLE_BYTES, seed=DUMP_SEED):
+    """The windows whose x / y ``dump_outputs`` writes: a seeded permutation of the batch, cut where the windows' x and
+    y reach ``budget`` bytes (float64), in ascending order.  Depends on the descriptors only."""
+    d = np.asarray(desc)
+    perm = np.random.default_rng(seed).permutation(len(d))
+    size = 8 * (d[perm, 0] + d[perm, 1])
+    k = int(np.searchsorted(np.cumsum(size), budget, side="right"))
+    return np.sort(perm[:max(k, min(1, len(d)))])
+
+
+def _segments(off, n):
+    """Indices off[i] .. off[i] + n[i] - 1 of every i, concatenated."""
+    tot = int(n.sum())
+    start = np.repeat(off - (np.cumsum(n) - n), n)
+    return start + np.arange(tot, dtype=np.int64)
+
+
+def dump_outputs(path, dev, desc, stats, istats, gathered=None, budget=DUMP_SAMPLE_BYTES):
+    """``--dump-outputs``: what the timed path left for its caller after the last timed step, as float64 .npy files:
+    stats [count, 4] (objective, primal / dual residual, gap) and istats [count, 2] (status, iterations) of every
+    window; sample_windows [k] and the sampled windows' concatenated primal / dual iterates x_sample, y_sample
+    (``dump_sample``; the whole x and y of the bench batch are several GB); N > 1: the sampled windows' gathered
+    result rows of rank 0's shard, gathered_sample."""
+    os.makedirs(path, exist_ok=True)
+    d = np.asarray(desc)
+    win = dump_sample(d, budget)
+    ix = torch.as_tensor(_segments(d[win, 6], d[win, 0]), device=dev.x.device)
+    iy = torch.as_tensor(_segments(d[win, 7], d[win, 1]), device=dev.y.device)
+    out = {"stats": stats, "istats": istats, "sample_windows": win,
+           "x_sample": dev.x[ix].cpu().numpy(), "y_sample": dev.y[iy].cpu().numpy()}
+    if gathered is not None:
+        out["gathered_sample"] = gathered[torch.as_tensor(win, device=gathered.device)].cpu().numpy()
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def stream_copy_gbps(dev, gib=2.0, reps=10):
     """Measured HBM copy ceiling on this GPU (torch device-to-device copy, read + write bytes / time)."""
     n = int(gib * 2 ** 30 / 8)
@@ -142,11 +191,13 @@ def roofline_object(alg, pdhg_s, prof, kname, launches, copy_gbps):
                                                    + c.get("SQ_INSTS_VALU_MUL_F64", 0.0)) / max(valu, 1.0), 4)}
         r["pmc_counters"] = "profiles/pdhg_valu.json"
     t = prof.get("pdhg_traffic")
-    hbm = {"peak": HBM_PEAK_GBS, "unit": "GB/s", "stream_copy": round(copy_gbps, 1)}
+    # copy_gbps None: the copy ceiling was not measured (a run without --full)
+    hbm = {"peak": HBM_PEAK_GBS, "unit": "GB/s", "stream_copy": None if copy_gbps is None else round(copy_gbps, 1)}
     if t and pdhg_s > 0:
         r["traffic"] = t["hbm_bytes_per_step"]
         a = t["hbm_bytes_per_step"] / pdhg_s / 1e9
-        hbm.update(achieved=round(a, 1), frac=round(a / HBM_PEAK_GBS, 5), frac_of_stream_copy=round(a / copy_gbps, 5),
+        hbm.update(achieved=round(a, 1), frac=round(a / HBM_PEAK_GBS, 5),
+                   frac_of_stream_copy=None if copy_gbps is None else round(a / copy_gbps, 5),
                    pmc_counters="profiles/pdhg_traffic.json (FETCH_SIZE x2 + WRITE_SIZE)")
     r["hbm"] = hbm
     r["effective"] = {"alg_bytes_per_step": alg, "GBps": round(alg / pdhg_s / 1e9, 1) if pdhg_s > 0 else None,
@@ -308,7 +359,14 @@ def main():
     ap.add_argument("--cpu-sample", type=int, default=960, help="windows in the HiGHS CPU-baseline sample")
     ap.add_argument("--cpu-procs", type=int, default=0)
     ap.add_argument("--cpu-pdhg-sample", type=int, default=960, help="windows in the C++ CPU PDHG baseline sample")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: the all-cold reference "
+                         "solve (schedule.cold_*), the CPU baselines with the HiGHS parity check (cpu_baseline, parity) "
+                         "and the measured HBM copy ceiling (roofline.hbm.stream_copy); a plain run reports them as null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy (float64): "
+                         "stats and istats of every window, x and y of a fixed seeded sample of windows")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines and the parity check")
     ap.add_argument("--check-every", type=int, default=0, help="restart-check period (0: library default)")
     ap.add_argument("--kkt-every", type=int, default=0, help="KKT check every n restart checks (0: default)")
     ap.add_argument("--schedule", choices=("seeded", "cold"), default="seeded",
@@ -323,7 +381,8 @@ def main():
                     help="> 0: blend weights moved toward the partners' affine combination that reproduces the window's "
                          "features, regularised toward the inverse-distance weights by LAM (dervet_hip.sweep."
                          "affine_weights); <= 0: inverse-distance weights")
-    ap.add_argument("--no-cold-ref", action="store_true", help="skip the untimed all-cold reference solve")
+    ap.add_argument("--no-cold-ref", action="store_true",
+                    help="with --full: skip the untimed all-cold reference solve")
     ap.add_argument("--sha", action="store_true", help="add the SHA-256 of the last step's x / y / stats / istats "
                     "(bit-identity of two library builds on the same batch)")
     ap.add_argument("--warm-options", default="", help="seeded schedule: dvh_options of the warm phase as JSON "
@@ -349,6 +408,8 @@ def main():
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # --gpus N without an outside launcher: N rank processes of this script, started before this process touches
         # the GPU (children, never an exec of this process)
@@ -549,7 +610,10 @@ def main():
     optimal_frac = float(np.mean(ist[:, 0] == 0))
     lps_step = 2 if sweep is not None and count > sweep.n_seed else 1
     prof = pmc_profiles(count, lps_step)
-    roofline = roofline_object(alg, pdhg_s, prof, kname, lps_step, stream_copy_gbps(local))
+    if args.dump_outputs and rank == 0:  # (before the cold reference solve overwrites the batch's outputs)
+        dump_outputs(args.dump_outputs, dev, desc, st, ist, gathered)
+    # the HBM copy ceiling is a measurement of its own (--full); the rest of the object comes from the timed steps
+    roofline = roofline_object(alg, pdhg_s, prof, kname, lps_step, stream_copy_gbps(local) if args.full else None)
 
     schedule = {"kind": args.schedule}
     if sweep is not None:
@@ -559,7 +623,7 @@ def main():
         schedule.update(seed_stride=args.seed_stride, blend=sweep.blend, seed_windows=ns, iters_mean_seed=round(float(iters[:ns].mean()), 1),
                         iters_mean_warm=round(float(iters[ns:].mean()), 1) if count > ns else None,
                         pdhg_launches_per_step=2 if count > ns else 1)
-    if sweep is not None and not args.no_cold_ref:
+    if args.full and sweep is not None and not args.no_cold_ref:
         # the same batch once more with every window started from zero (untimed by the contract; for reference)
         st_seeded = st[:, 0].copy()
         solver.set_options(warm_start=0)
@@ -578,7 +642,7 @@ def main():
 
     cpu = None
     parity = None
-    if rank == 0 and world == 1 and not args.no_cpu and args.cpu_sample > 0:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu and args.cpu_sample > 0:
         from oracle import cba, cpu_baseline, window_lp
         idx = np.linspace(0, count - 1, min(args.cpu_sample, count)).astype(np.int64)
         lps = [window_lp.from_packed_window(pb.window(int(k))) for k in idx]
