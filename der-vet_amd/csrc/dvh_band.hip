@@ -18,9 +18,15 @@
 // SOE / DCM (/ ICE) rows -- with every coefficient, bound, objective, iterate and anchor in VGPRs.  An SpMV needs
 // only the next step's ene (K x) and the previous SOE row's dual (K^T y); inside a lane those are registers, across
 // lanes one LDS store + one LDS load per lane and half-step.  The dense tau columns are summed by wave 0 from
-// per-lane partials.  Instantiations: <768, 1> (one step per lane, 12 waves, one window per CU) and <384, 2> (two
-// steps per lane, 6 waves: two windows share a CU, so one window's barrier waits are filled by the other's work,
-// and every lane carries two independent FMA chains).  <= 168 VGPRs (3 waves per SIMD) either way.
+// per-lane partials.  Three forms are instantiated (launch_pdhg_band, at the end of the file):
+//   <256, 3> battery  three steps per lane, 4 waves = one per SIMD, about 252 VGPRs (2 waves per SIMD), costs and
+//                     right-hand sides in LDS: two windows share a CU, so one window's barrier waits are filled by the
+//                     other's work.  The default; persistent grid (dvh_band_persist.hip).
+//   <768, 1> battery  one step per lane, 12 waves, one window per CU: batches of at most one window per CU
+//                     (dvh_api.cpp picks the form by batch size), one workgroup per window.
+//   <768, 1> ICE      one step per lane at a 168-VGPR budget (3 waves per SIMD; twice the per-step state, the ICE
+//                     columns' and rows' read-only data in LDS).  Persistent grid (dvh_band_persist_ice.hip).
+// What was measured and not kept in this kernel is listed in DESIGN.md section 4, "Measured and not kept (band kernel)".
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -36,76 +42,67 @@ constexpr int kBandSteps = 768;  // steps per window (T <= kBandSteps)
 constexpr int kJMax = 4;         // tau (demand-period) columns per window
 constexpr int kNeedsEll = -2;
 
-// LDS layout (B lanes, S steps per lane, SB = S B steps), doubles then ints:
-//   XE[B+1] YS[B+1] XT[kJMax] red[kNRed(NW+1)+4] TP[kJMax][B] XP[NC S][B] YP[NR S][B] (ICE: RO[6 S][B])
-//   | ints: dcm[SB] ice_a[SB] ice_b[SB] ice_n[SB] flag[4]
-// Register-relief flags LF (forms with several steps per lane): kLfAnchors -- the Halpern anchors XA[NC S][B] /
-// YA[NR S][B] live in LDS (one FMA operand per iteration, written at restarts; the ints, read only while the lane
-// state is loaded, share their space); kLfCosts -- CQ[5 S][B] = c of ch / dis / ene and q of the SOE / DCM rows in
-// LDS (one FMA addend per iteration); kLfImages -- the check iteration's T(z_k) goes to the window's global workspace
-// instead of XP / YP (read back by the same lane at the check).  Layout after TP: [XP YP] (no kLfImages) [XA YA]
-// (kLfAnchors) [RO] (ICE) [CQ] (kLfCosts).
-constexpr int kLfAnchors = 1, kLfCosts = 2, kLfImages = 4;
-#ifndef DVH_BAND_TAU_WAVESUMS
-#define DVH_BAND_TAU_WAVESUMS 0
-#endif
-// tau_parts (below): per-wave sums of one tau column.  Off: the same-box bench A/B found no difference (227.5k vs
-// 227.7k windows/s, profiles/r04g_ab_band_tau_wavesums.log); the round-3 arithmetic (certified) is kept.
-constexpr bool kTauWaveSums = DVH_BAND_TAU_WAVESUMS != 0;
-// Where the band iteration's time goes (round 5): wave 0 reduces and updates the single tau column of a monthly window
-// (J = 1) at the start of the primal half-step, and the other waves wait for it at the first barrier -- per wave
-// (scripts/probe_band_latency.py, profiles/r05b_band_latency.log) wave 0's primal half-step takes 996-1024 shader cycles
-// against 610-640 for the others, who wait 390-440 cycles there.  Measured and not kept (profiles/r05c_*, r05g_*): a
-// replica of the column in every wave updated in the primal half-step (1.099 vs 1.048 us per window-iteration per
-// slot) and the column updated in the dual half-step by every wave (1.146): every wave then carries the chain; the
-// costs read from LDS ahead of the second barrier (1.136: the compiler holds them through the iteration).  Ablations at
-// a fixed iteration count (wrong results; profiles/r05h_band_ablations.log, r05k_*) bound what is left: without the tau
-// chain -7 %, without both barriers -9 %, without the cost / right-hand-side LDS reads -7.5 %, all together -24 %.
-__host__ __device__ inline size_t band_lds_doubles(int B, int S, bool ice, int LF) {
+// LDS layout (B lanes, S steps per lane, SB = S B steps; NC / NR = columns / rows per step), doubles then ints:
+//   XE[B+1] YS[B+1] XT[kJMax] red[kNRed(NW+1)+4] TP[kJMax][B] XP[NC S][B] YP[NR S][B] (ICE: RO[6 S][B]) (LC: CQ[5 S][B])
+//   | ints: dcm[SB] ice_a[SB] ice_b[SB] ice_n[SB] flag[4] | DRL[S][B]
+// LC (the three-step form): CQ = c of ch / dis / ene and q of the SOE / DCM rows in LDS instead of VGPRs (one FMA
+// addend per iteration), and the ints, read only during the set-up, share the check images' space XP / YP, so that two
+// windows fit one CU's LDS.  DRL: the lane's DCM row indices, kept in LDS from the set-up to the write-back (held in
+// VGPRs across the iteration loop they were among the persistent form's spilled values).
+__host__ __device__ constexpr size_t band_lds_doubles(int B, int S, bool ice, bool lc) {
   const int NW = B / kWave, NC = ice ? 5 : 3, NR = ice ? 4 : 2;
   const size_t SB = (size_t)S * B;
-  return 2 * (size_t)(B + 1) + kJMax + (size_t)kNRed * (NW + 1) + 4 + (size_t)kJMax * B +
-         ((LF & kLfImages) ? 0 : (NC + NR) * SB) + ((LF & kLfAnchors) ? (NC + NR) * SB : 0) +
-         ((LF & kLfCosts) ? 5 * SB : 0) + (ice ? 6 * SB : 0);
+  return 2 * (size_t)(B + 1) + kJMax + (size_t)kNRed * (NW + 1) + 4 + (size_t)kJMax * B + (NC + NR) * SB +
+         (lc ? 5 * SB : 0) + (ice ? 6 * SB : 0);
 }
-__host__ __device__ inline size_t band_ints_bytes(int B, int S) { return sizeof(int32_t) * (4 * (size_t)S * B + 4); }
-// The ints share the anchors' (kLfAnchors) or, in the other relieved forms, the check images' space
-__host__ __device__ constexpr bool band_ints_shared(int LF) { return (LF & kLfAnchors) || (LF && !(LF & kLfImages)); }
-// (round 6) the lane's DCM row indices, drow[S][B], kept in LDS from the set-up to the write-back instead of in VGPRs (held
-// across the iteration loop they were among the persistent form's spilled values, and each check's reload of a spilled
-// index waited for every global load issued before it)
-__host__ __device__ inline size_t band_drow_bytes(int B, int S) { return align16(sizeof(int32_t) * (size_t)S * B); }
-__host__ __device__ inline size_t band_lds_bytes(int B, int S, bool ice, int LF) {
-  const size_t d = align16(sizeof(double) * band_lds_doubles(B, S, ice, LF));
-  return (band_ints_shared(LF) ? d : d + align16(band_ints_bytes(B, S))) + band_drow_bytes(B, S);
+__host__ __device__ constexpr size_t band_ints_bytes(int B, int S) { return sizeof(int32_t) * (4 * (size_t)S * B + 4); }
+__host__ __device__ constexpr size_t band_drow_bytes(int B, int S) { return align16(sizeof(int32_t) * (size_t)S * B); }
+__host__ __device__ constexpr size_t band_lds_bytes(int B, int S, bool ice, bool lc) {
+  const size_t d = align16(sizeof(double) * band_lds_doubles(B, S, ice, lc));
+  return (lc ? d : d + align16(band_ints_bytes(B, S))) + band_drow_bytes(B, S);
 }
+static_assert(band_lds_bytes(kBandSteps / 3, 3, false, true) == 77328, "three-step battery form: two windows per CU");
+static_assert(band_lds_bytes(kBandSteps, 1, false, false) == 84192, "one-step battery form");
+static_assert(band_lds_bytes(kBandSteps, 1, true, false) == 145632, "ICE form");
 
-// KKT pieces of one column / one row (out of line: the KKT check runs every 128 iterations, and inlined it
-// would raise the whole kernel's register allocation).  Scale-free where the check compares large terms: the
-// objectives' sums c'x, q'y and the bound term l'lam+ + u'lam- are the same in the scaled space (c~ x~ = c x,
-// l~ lam~ = (l / d)(d lam) with lam~ = c~ - K~'y~ the scaled reduced cost, d > 0 keeping its sign), so the gap needs
-// no factor at all.  Only the residual norms and ||y|| are unscaled, with fd = the factor in single precision
-// (Work::fc / fr) and a 1-ulp v_rcp_f32 reciprocal: each term moves by a relative 2e-7 at most, i.e. each norm by a
-// relative 2e-7 of itself.  The outputs are unscaled with the exact factors.
-// DVH_KKT_INLINE: 1 (default) the KKT helpers below inlined into the battery forms and called out of line from the ICE
-// form; 2 inlined everywhere; 0 out of line everywhere (rounds 1-4, so as not to raise the kernel's register
-// allocation).  Out of line, every call binds the caller's live registers to the call ABI: inlined, the persistent
-// battery form runs 1.5 % faster per iteration with no checks at all and 0.8-1.2 % on the sweep's check schedules
-// (profiles/r05s_check_cost_*.log).  The ICE form (168-VGPR budget, already spilling) runs config 5 5.6 % slower with
-// them inlined (106.5k vs 112.9k windows/s, identical iterations; profiles/r05za_config5_bisect.log), although a
-// fixed-iteration run with checks that never converge had it 9.4 % faster (profiles/r05u_kkt_inline_ice_chain.log).
-#ifndef DVH_KKT_INLINE
-#define DVH_KKT_INLINE 1
-#endif
+// How the ICE form (168-VGPR budget, already spilling) differs from the battery forms.
 template <bool ICE>
-constexpr bool kkt_inline() { return DVH_KKT_INLINE == 2 || (DVH_KKT_INLINE == 1 && !ICE); }
+struct BandTune {
+  // the KKT helpers below inlined into the check (out of line every call binds the caller's live registers to the call
+  // ABI; battery +0.8-1.5 %, profiles/r05s_check_cost_*.log; ICE -5.6 % inlined, profiles/r05za_config5_bisect.log)
+  static constexpr bool kkt_inline = !ICE;
+  // a check's single-precision factors loaded together at its top, one wait instead of 15 serialised global-memory
+  // latencies (ICE: 14 more spilled VGPRs, config 5 111.9k vs 114.7k windows/s, profiles/r06c_ab.log)
+  static constexpr bool kkt_prefetch = !ICE;
+  // the waves without the tau column finish their own-column K x-bar before the first barrier, where they wait for
+  // wave 0 anyway (ICE 116.5k -> 126.0k; battery within its spread at +10 spilled VGPRs, profiles/r06l_pin_kx.log)
+  static constexpr bool pin_kx = ICE;
+  // the check path's wave-uniform doubles through v_readfirstlane, held in SGPR pairs between checks (ICE spills
+  // 41 -> 19, config 5 +1.3 %; battery 1.8 % slower, profiles/r06r_uscal.log)
+  static constexpr bool uniform_check_scalars = ICE;
+  // the objective gate's dual-residual term sum_j |r_d,j| |x_j| (kkt_done; the extra reduced value cost the ICE form
+  // 6 % on config 5 at unchanged iterations, profiles/r04ab_ab_kkt_rdx.log: its windows keep the round-3 test)
+  static constexpr bool gate_rdx = !ICE;
+};
+// Wave 0, whose primal half-step carries the tau column's reduction and update -- the iteration's critical path, on
+// which the other waves wait at the first barrier -- runs that half-step at this s_setprio level, so that the SIMD it
+// shares with the other window's wave issues its instructions first (profiles/r06a_ab.log).
+constexpr int kTauWavePrio = 2;
+
+// KKT pieces of one column / one row.  Scale-free where the check compares large terms: the objectives' sums c'x, q'y
+// and the bound term l'lam+ + u'lam- are the same in the scaled space (c~ x~ = c x, l~ lam~ = (l / d)(d lam) with
+// lam~ = c~ - K~'y~ the scaled reduced cost, d > 0 keeping its sign), so the gap needs no factor at all.  Only the
+// residual norms and ||y|| are unscaled, with fd = the factor in single precision (Work::fc / fr) and a 1-ulp
+// v_rcp_f32 reciprocal: each term moves by a relative 2e-7 at most, i.e. each norm by a relative 2e-7 of itself.  The
+// outputs are unscaled with the exact factors.
+// _i: inlined (BandTune::kkt_inline); _o: out of line, so that the check does not raise the kernel's register allocation.
 struct ColKkt {
   double rd2, cx, bt;
 };
 struct ColKktX : ColKkt {
-  double rdx;  // |r_d| |x| of the column, unscaled (the battery forms' objective gate)
+  double rdx;  // |r_d| |x| of the column, unscaled (BandTune::gate_rdx)
 };
-__device__ __forceinline__ ColKkt col_kkt_i(double kt, double cj, double loj, double hij, double xj, float fd) {
+__device__ __noinline__ ColKkt col_kkt_o(double kt, double cj, double loj, double hij, double xj, float fd) {
   const double id = (double)__builtin_amdgcn_rcpf(fd);
   const double rs = cj - kt;  // scaled reduced cost
   const bool fl = isfinite(loj), fh = isfinite(hij);
@@ -135,24 +132,8 @@ __device__ __forceinline__ RowKkt row_kkt_i(double kv, double qi, double yi, flo
   if (ge) r = fmax(r, 0.0);
   return {r * r, (yi * dr) * (yi * dr)};
 }
-__device__ __noinline__ ColKkt col_kkt_o(double kt, double cj, double loj, double hij, double xj, float fd) {
-  return col_kkt_i(kt, cj, loj, hij, xj, fd);
-}
-__device__ __noinline__ ColKktX col_kkt_x_o(double kt, double cj, double loj, double hij, double xj, float fd) {
-  return col_kkt_x_i(kt, cj, loj, hij, xj, fd);
-}
 __device__ __noinline__ RowKkt row_kkt_o(double kv, double qi, double yi, float fd, int ge) {
   return row_kkt_i(kv, qi, yi, fd, ge);
-}
-template <bool INL>
-__device__ __forceinline__ ColKkt col_kkt_fn(double kt, double cj, double loj, double hij, double xj, float fd) {
-  if constexpr (INL) return col_kkt_i(kt, cj, loj, hij, xj, fd);
-  else return col_kkt_o(kt, cj, loj, hij, xj, fd);
-}
-template <bool INL>
-__device__ __forceinline__ ColKktX col_kkt_fn_x(double kt, double cj, double loj, double hij, double xj, float fd) {
-  if constexpr (INL) return col_kkt_x_i(kt, cj, loj, hij, xj, fd);
-  else return col_kkt_x_o(kt, cj, loj, hij, xj, fd);
 }
 template <bool INL>
 __device__ __forceinline__ RowKkt row_kkt_fn(double kv, double qi, double yi, float fd, int ge) {
@@ -173,109 +154,11 @@ __device__ __forceinline__ RowKkt row_kkt_fn(double kv, double qi, double yi, fl
 // primed LP, whose objectives, row residuals and (zero, for a two-sided box) column residuals equal the original's
 // once the constant c lo is added.  A window with an unbounded ch / dis / ene (/ elec / on) column is returned with
 // status kNeedsPlain and re-run by the plain form (dvh_api.cpp device_cascade).
+// The widths w are kept nowhere: the per-column steps tau / w^2 are formed from the registers at the box set-up, a
+// restart rescales them by tau_new / tau_old (one uniform quotient, no per-column division), the check iteration's
+// movement norms weigh each column's d'^2 by w^2 = tau / step (an approximate reciprocal: the norms only steer restarts
+// and the primal weight), and the write-back recomputes w = u / d - l / d with the set-up's operations (bit-identical).
 constexpr int kNeedsPlain = -3;
-// kBoxRescale (box form): the checks and restarts stop re-reading the columns' box widths from the window's workspace
-// in HBM.  A restart rescales the per-column steps tau / w^2 by tau_new / tau_old (one uniform quotient, no per-column
-// division), and the check iteration's movement norms, in x units, weigh each column's d'^2 by w^2 = tau / step (an
-// approximate reciprocal: the norms only steer restarts and the primal weight).  Before, each check iteration loaded
-// the 9 widths of its three steps and each restart loaded them again and divided 9 times.
-#ifndef DVH_BAND_RSTEP
-#define DVH_BAND_RSTEP 1
-#endif
-constexpr bool kBoxRescale = DVH_BAND_RSTEP != 0;
-// kNoWidths (round 6, box form): the columns' widths are not kept in the window's workspace -- the steps are formed
-// from the registers at set-up, the restarts rescale them (kBoxRescale), and the write-back recomputes w = u / d - l / d
-// with the operations of the set-up (bit-identical): one write and one read of 8 bytes per column less per window.
-#ifndef DVH_BAND_NOWIDTHS
-#define DVH_BAND_NOWIDTHS 1
-#endif
-constexpr bool kNoWidths = kBoxRescale && DVH_BAND_NOWIDTHS != 0;
-// DVH_BAND_F32F (A/B, off): the Ruiz / Pock-Chambolle factors rounded to single precision once, when the scaling passes
-// end (1: the outputs unscaled from the single-precision copy, which is then the factor exactly, and the factors no
-// longer written in double; -1: rounded only).  Measured and not kept (profiles/r06b_t2_rounded_factors.log): the
-// degenerate two-step window of tests/test_gpu_configs.py::test_band_kernel_forms_agree[2] (two demand periods of one
-// step each) converges in 10,496 / 3,968 iterations (three-step / one-step form) with the exact factors and not at all
-// (20,000) with the rounded ones -- a 1e-8 change of the preconditioner moves PDHG's path on that window that much.
-#ifndef DVH_BAND_F32F
-#define DVH_BAND_F32F 0
-#endif
-constexpr bool kF32Factors = DVH_BAND_F32F > 0;
-constexpr bool kF32Round = kF32Factors || DVH_BAND_F32F == -1;
-// kHalpernDiv (round 6): the 64 Halpern weights 1 / (k + 2) of the next block of iterations are divided in the lanes
-// (one correctly rounded quotient per lane: the table's values, bit for bit) instead of loaded from the global table.
-// The load sat on the restart path: a restart resets k to 0 and the very next iteration reads weight 0, so every
-// restart waited for a global load (and the table pointer was one of the values the persistent loop spilled).
-#ifndef DVH_BAND_HDIV
-#define DVH_BAND_HDIV 1
-#endif
-constexpr bool kHalpernDiv = DVH_BAND_HDIV != 0;
-// kkt_prefetch (round 6): a KKT check reads the single-precision factors of the lane's columns and rows (Work::fc / fr,
-// 15 per lane) from the window's workspace.  Each load sat behind its opaque index (kept so that the check's address
-// arithmetic is not hoisted into the iteration loop) and was waited for before the next one was issued: 15 serialised
-// global-memory latencies per check (the ISA showed each global_load_dword followed by s_waitcnt vmcnt(0)).  Now the
-// indices and loads are issued together at the top of the check, one wait behind the image reads and the barrier.
-#ifndef DVH_BAND_KKT_PREFETCH
-#define DVH_BAND_KKT_PREFETCH 1
-#endif
-// (the ICE form, at its 168-VGPR budget, spills 14 VGPRs more with the batched loads and runs config 5 slower: 111.9k vs
-// 114.7k windows/s, profiles/r06c_ab.log -- it keeps the per-use loads)
-#ifndef DVH_BAND_KKT_PREFETCH_ICE
-#define DVH_BAND_KKT_PREFETCH_ICE 0
-#endif
-template <bool ICE>
-constexpr bool kkt_prefetch() { return DVH_BAND_KKT_PREFETCH != 0 && (!ICE || DVH_BAND_KKT_PREFETCH_ICE != 0); }
-// DVH_BAND_PRIO (round 6, default 2): wave 0, whose primal half-step carries the tau column's reduction and update --
-// the iteration's critical path, on which the other three waves wait at the first barrier -- raises its issue priority
-// (s_setprio) until that barrier, so that the SIMD it shares with the other window's wave issues its instructions
-// first.  Measured (scripts/gpu_r06a.sh, profiles/r06a_ab.log): 0.979 -> 0.940 us per window-iteration per slot at a
-// fixed 1,024 iterations, bench 284.4k -> 292.9k windows/s, identical iterations and residuals; config 5 (the ICE form,
-// whose wave 0 of twelve carries the column) 108.3k -> 111.9k (profiles/r06c_ab.log).  0: off.
-#ifndef DVH_BAND_PRIO
-#define DVH_BAND_PRIO 2
-#endif
-// (DVH_BAND_PRIO_SETUP, A/B, off) the same for the set-up's tau reductions on wave 0 (every scaling pass and power-iteration
-// step): measured slower, 290.2k vs 292.3k windows/s (profiles/r06i_prio_setup.log) -- there the raised wave takes issue
-// slots from the other window's iterations
-#ifndef DVH_BAND_PRIO_SETUP
-#define DVH_BAND_PRIO_SETUP 0
-#endif
-constexpr bool kPrioSetup = DVH_BAND_PRIO_SETUP != 0;
-// DVH_BAND_PRIO_DUAL (A/B): every wave raises its priority from the start of the dual half-step until its DCM rows'
-// tau partials are written (the values wave 0's next reduction waits for).  Measured and not kept: 292.0k vs 292.6k
-// windows/s (profiles/r06c_ab.log); s_setprio 3 instead of 2 for wave 0: 292.7k (same).
-// DVH_BAND_PIN_BLEND (A/B): wave 0 finishes the iteration's Halpern blends (x = ca x-bar + cb x-anchor, and the rows')
-// before the second barrier, where it waits for the others anyway, instead of after it: the compiler sank them past the
-// barrier, to the head of wave 0's next primal half-step -- in front of the tau reduction, at normal priority.
-// Measured (profiles/r06j_pin_blend.log): bench 293.1k -> 298.1k windows/s, 0.939 -> 0.930 us per window-iteration per
-// slot at a fixed 1,024 iterations, identical iterations and residuals.
-#ifndef DVH_BAND_PIN_BLEND
-#define DVH_BAND_PIN_BLEND 1
-#endif
-// DVH_BAND_LATE_SOE: the waves without the tau column update the SOE rows of their lanes' steps 0 .. S - 2 after the
-// second barrier instead of before it (those duals are read only by the lane's own next primal half-step), so that they
-// reach the barrier -- which wave 0's next tau reduction waits behind -- sooner.  With 15 spilled VGPRs it was within the
-// bench's spread (298.7k vs 297.9k, profiles/r06k_late_soe.log); with the spills gone (DVH_BAND_UWIN) bench 300.1k ->
-// 304.6k windows/s, config 5 unchanged (profiles/r06s_ab.log).
-// DVH_BAND_PIN_KX (A/B): the waves without the tau column finish their primal half-step's own-column K x-bar (x-bar =
-// 2 p - x, then K x-bar - q of their rows) before the first barrier, where they wait for wave 0 anyway, instead of after
-// it: the compiler sank that work into their dual half-step, which is the critical path into the second barrier.
-// Measured (profiles/r06l_pin_kx.log): config 5 (the ICE form: eleven such waves) 116.5k -> 126.0k windows/s; the bench
-// 298.2k -> 298.6k, within its spread, at 25 instead of 15 spilled VGPRs.  1 (default): the ICE form only; 2: every form.
-#ifndef DVH_BAND_PIN_KX
-#define DVH_BAND_PIN_KX 1
-#endif
-// DVH_BAND_LATE_ICE: the same waves update the two ICE rows' duals (read only by the lane's own next primal
-// half-step) after the second barrier instead of before it.  Measured (profiles/r06m_late_ice.log): config 5
-// 126.0k -> 127.9-128.4k windows/s.
-#ifndef DVH_BAND_LATE_ICE
-#define DVH_BAND_LATE_ICE 1
-#endif
-#ifndef DVH_BAND_LATE_SOE
-#define DVH_BAND_LATE_SOE 1
-#endif
-#ifndef DVH_BAND_PRIO_DUAL
-#define DVH_BAND_PRIO_DUAL 0
-#endif
 // DVH_BAND_PROBE (A/B builds only, scripts/probe_band_latency.py): every wave accumulates the shader-clock cycles of
 // its iterations' four segments -- primal half-step, wait at the first barrier, dual half-step, wait at the second --
 // and of the checks, and lane 0 writes them over x[6 wid .. 6 wid + 4] of its window at the end, with the wave's
@@ -296,44 +179,34 @@ __device__ __forceinline__ double fma_clamp01(double a, double b, double c) {
   return r;
 }
 
-// DVH_BAND_UWIN: the window index and its descriptor's offsets are read through v_readfirstlane, so that they and every
-// address formed from them (the window's CSR, costs, bounds, outputs, workspace) are scalar.  Loaded as they are -- with
-// vector loads, since the kernel writes global memory the compiler does not treat the descriptors as constant -- they sat
-// in VGPR pairs, and the base addresses the set-up and the write-back use were spilled.
-#ifndef DVH_BAND_UWIN
-#define DVH_BAND_UWIN 1
-#endif
-// DVH_BAND_USCAL: the check path's wave-uniform doubles (the fixed-point residual and the restart test's r0 / rprev, the
-// KKT objectives and ratios, the gate's state) through v_readfirstlane, and the residuals' denominators formed where they
-// are used: held in SGPR pairs between checks instead of VGPR pairs.  1 (default): the ICE form only -- at its 168-VGPR
-// budget spilled VGPRs 41 -> 19, config 5 +1.3 %; in the battery form (spills 2 -> 0) the bench ran 1.8 % slower
-// (profiles/r06r_uscal.log); 2: every form.
-#ifndef DVH_BAND_USCAL
-#define DVH_BAND_USCAL 1
-#endif
+// a check-path wave-uniform double, made scalar where BandTune says so
 template <bool ICE>
 __device__ __forceinline__ double usc(double v) {
-  return (DVH_BAND_USCAL > 1 || (DVH_BAND_USCAL == 1 && ICE)) ? uniform(v) : v;
+  return BandTune<ICE>::uniform_check_scalars ? uniform(v) : v;
 }
 // a uniform double the optimiser must re-read where it is used (so that what is formed from it is not hoisted out of the
 // iteration loop into a long-lived VGPR pair)
 template <bool ICE>
 __device__ __forceinline__ double sgpr_fresh(double v) {
-  if constexpr (DVH_BAND_USCAL > 1 || (DVH_BAND_USCAL == 1 && ICE)) asm volatile("" : "+s"(v));
+  if constexpr (BandTune<ICE>::uniform_check_scalars) asm volatile("" : "+s"(v));
   return v;
 }
-template <int B, int S, bool ICE, int LF, int WPS, bool GATE, bool BOX>
+template <int B, int S, bool ICE, bool LC, int WPS, bool GATE, bool BOX>
 __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const Chunk& ch, const Opts& o, const int k_in,
                                             const int tid) {
-  const int k = DVH_BAND_UWIN ? __builtin_amdgcn_readfirstlane(k_in) : k_in;
-  static_assert(!BOX || !(LF & kLfImages), "the box form keeps the check images in LDS");
+  // the window index and its descriptor's offsets through v_readfirstlane, so that they and every address formed from
+  // them (the window's CSR, costs, bounds, outputs, workspace) are scalar: loaded as they are -- with vector loads, since
+  // the kernel writes global memory the compiler does not treat the descriptors as constant -- they sat in VGPR pairs,
+  // and the base addresses the set-up and the write-back use were spilled
+  const int k = __builtin_amdgcn_readfirstlane(k_in);
+  using Tune = BandTune<ICE>;
   constexpr int NW = B / kWave;
   constexpr int SB = S * B;        // step capacity
   constexpr int NC = ICE ? 5 : 3;  // columns per step: ch, dis, ene (, elec, on)
   constexpr int NR = ICE ? 4 : 2;  // rows per step: SOE, DCM (, ICE rated, ICE minimum)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int kl = k - ch.first;
-  const WinOff W = DVH_BAND_UWIN ? uniform_win(win_offsets(b, ch, k)) : win_offsets(b, ch, k);
+  const WinOff W = uniform_win(win_offsets(b, ch, k));
   const int n = W.n, m = W.m, meq = W.meq;
   const int lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   double* scal = w.scal + (int64_t)kl * kScal;
@@ -359,26 +232,21 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
   double* XT = YS + (B + 1);  // x-bar (x+) of the tau columns
   double* red = XT + kJMax;
   double* TP = red + kNRed * (NW + 1) + 4;  // [kJMax][B] per-lane partial K'y of the tau columns
-  constexpr bool LA = LF & kLfAnchors, LC = LF & kLfCosts, LI = LF & kLfImages;
-  double* XP = TP + kJMax * B;                  // [NC S][B] T(z) of the lane's columns (check iterations)
-  double* YP = XP + (LI ? 0 : NC * SB);         // [NR S][B] T(z) of the lane's rows
-  double* XA = YP + (LI ? 0 : NR * SB);         // [NC S][B] Halpern anchors of the columns (kLfAnchors)
-  double* YA = XA + (LA ? NC * SB : 0);         // [NR S][B] and of the rows
+  double* XP = TP + kJMax * B;  // [NC S][B] T(z) of the lane's columns (check iterations)
+  double* YP = XP + NC * SB;    // [NR S][B] T(z) of the lane's rows
   // ICE: read-only data of the ICE columns / rows in LDS instead of VGPRs (the register budget at 3 waves per
   // SIMD is 168): RO[0..1] = c of elec / on, RO[2..3] = upper bound of elec / on, RO[4..5] = q of the two ICE rows,
   // each [S][B]
-  double* RO = YA + (LA ? NR * SB : 0);
-  double* CQ = RO + (ICE ? 6 * SB : 0);  // [5 S][B] (kLfCosts)
-  static_assert(!LA || sizeof(double) * (NC + NR) * SB >= sizeof(int32_t) * (4 * SB + 4), "ints fit the anchors");
-  constexpr bool IS = band_ints_shared(LF);  // the ints share the anchors' / images' LDS
-  int32_t* dcm = LA   ? reinterpret_cast<int32_t*>(XA)
-                 : IS ? reinterpret_cast<int32_t*>(XP)
-                      : reinterpret_cast<int32_t*>(smem + align16(sizeof(double) * band_lds_doubles(B, S, ICE, LF)));
+  double* RO = YP + NR * SB;
+  double* CQ = RO + (ICE ? 6 * SB : 0);  // [5 S][B] (LC)
+  static_assert(sizeof(double) * (NC + NR) * SB >= band_ints_bytes(B, S), "the ints fit the images");
+  int32_t* dcm = LC ? reinterpret_cast<int32_t*>(XP)  // (LC) the ints share the images' LDS
+                    : reinterpret_cast<int32_t*>(smem + align16(sizeof(double) * band_lds_doubles(B, S, ICE, LC)));
   int32_t* ice_a = dcm + SB;  // [SB] ICE rows of each step (lower / higher row index), and their count
   int32_t* ice_b = ice_a + SB;
   int32_t* ice_n = ice_b + SB;
   int32_t* flag = ice_n + SB;
-  int32_t* DRL = reinterpret_cast<int32_t*>(smem + band_lds_bytes(B, S, ICE, LF) - band_drow_bytes(B, S));  // [S][B]
+  int32_t* DRL = reinterpret_cast<int32_t*>(smem + band_lds_bytes(B, S, ICE, LC) - band_drow_bytes(B, S));  // [S][B]
 
   const int32_t* gkp = b.indptr + W.row;
   const int32_t* gkc = b.indices + W.nz;
@@ -387,11 +255,12 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
   const double* lraw = b.l + W.on;
   const double* uraw = b.u + W.on;
   const double* qraw = b.q + W.om;
-  double* dcv = w.dc + W.wn;  // the factors this kernel computes (outputs are unscaled with them; !kF32Factors)
+  double* dcv = w.dc + W.wn;  // the factors this kernel computes (the outputs are unscaled with them)
   double* drv = w.dr + W.wm;
-  // the factor of column j / row i at the write-back: the single-precision copy is the factor itself (kF32Factors)
-  auto dcf = [&](int j) -> double { return kF32Factors ? (double)w.fc[W.wn + j] : dcv[j]; };
-  auto drf = [&](int i) -> double { return kF32Factors ? (double)w.fr[W.wm + i] : drv[i]; };
+  // the factor of column j / row i at the write-back (kept as lambdas: with plain dcv[j] / drv[i] there the one-step
+  // battery kernels come out with two SGPRs exchanged, and the certified machine code is kept bit for bit)
+  auto dcf = [&](int j) -> double { return dcv[j]; };
+  auto drf = [&](int i) -> double { return drv[i]; };
   double* xo_g = b.x + W.on;
   double* yo_g = b.y + W.om;
 
@@ -673,7 +542,6 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
     if (ilane) nsp = fabs(kin0) * fsp * XE[0];
     __syncthreads();
     if (wid == 0) {
-      if (DVH_BAND_PRIO && kPrioSetup) __builtin_amdgcn_s_setprio(DVH_BAND_PRIO);
       for (int j = 0; j < J; ++j) {
         double a = TP[j * B + lane];
 #pragma unroll
@@ -691,22 +559,10 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
     }
     if (tlane || ilane) fsp *= factor(nsp);
     __syncthreads();  // every read of this pass's XE / YS / XT / TP is done
-    if (DVH_BAND_PRIO && kPrioSetup && wid == 0) __builtin_amdgcn_s_setprio(0);
   }
   {  // the KKT checks unscale with single-precision copies of the factors: a window whose factors leave
      // [2^-100, 2^100] (far inside float's normal range) goes to the ELL / generic path, which keeps them in double
     auto oor = [](double f) { return !(f >= 0x1p-100 && f <= 0x1p100); };
-    if constexpr (kF32Round) {  // (round 6) every factor rounded to single precision once, here: the float copy in
-                                  // the workspace is then the factor itself, exactly
-#pragma unroll
-      for (int s = 0; s < S; ++s) {
-#pragma unroll
-        for (int v = 0; v < NC; ++v) fcv[s][v] = (double)(float)fcv[s][v];
-#pragma unroll
-        for (int r = 0; r < NR; ++r) frv[s][r] = (double)(float)frv[s][r];
-      }
-      fsp = (double)(float)fsp;
-    }
     bool out = oor(fsp);
 #pragma unroll
     for (int s = 0; s < S; ++s) {
@@ -774,7 +630,7 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
       x[s][v] = xa[s][v] = fmin(fmax(o.warm ? xo_g[j] / d : 0.0, lsj), usj);
       nrm[0] += csj * csj;
       nrm[2] += cj * cj;
-      if constexpr (!kF32Factors) dcv[j] = d;
+      dcv[j] = d;
       w.fc[W.wn + j] = (float)d;
     }
 #pragma unroll
@@ -798,7 +654,7 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
       if (o.warm) y[s][r] = ya[s][r] = r == 0 ? yo_g[i] / d : fmax(yo_g[i] / d, 0.0);
       nrm[1] += qsi * qsi;
       nrm[3] += qi * qi;
-      if constexpr (!kF32Factors) drv[i] = d;
+      drv[i] = d;
       w.fr[W.wm + i] = (float)d;
     }
   }
@@ -811,7 +667,7 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
     sp[4] = h0;
     nrm[0] += sp[2] * sp[2];
     nrm[2] += cj * cj;
-    if constexpr (!kF32Factors) dcv[j] = fsp;
+    dcv[j] = fsp;
     w.fc[W.wn + j] = (float)fsp;
   }
   if (ilane) {
@@ -821,7 +677,7 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
     if (o.warm) sp[0] = sp[1] = sp[2] = yo_g[0] / fsp;
     nrm[1] += sp[3] * sp[3];
     nrm[3] += q0 * q0;
-    if constexpr (!kF32Factors) drv[0] = fsp;
+    drv[0] = fsp;
     w.fr[W.wm] = (float)fsp;
   }
   block_sum<B, 4>(nrm, red);
@@ -830,40 +686,20 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
   int xta[S];
 #pragma unroll
   for (int s = 0; s < S; ++s) xta[s] = lds_addr(XT + jt[s]);
-  if constexpr (IS) __syncthreads();  // anchors / images overwrite the step -> row maps: every lane has read them
-  if constexpr (LA) {
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-#pragma unroll
-      for (int v = 0; v < NC; ++v) XA[(v * S + s) * B + tid] = xa[s][v];
-#pragma unroll
-      for (int r = 0; r < NR; ++r) YA[(r * S + s) * B + tid] = ya[s][r];
-    }
-  }
-  auto axv = [&](int s, int v) -> double { return LA ? XA[(v * S + s) * B + tid] : xa[s][v]; };
-  auto ayv = [&](int s, int r) -> double { return LA ? YA[(r * S + s) * B + tid] : ya[s][r]; };
+  if constexpr (LC) __syncthreads();  // the images overwrite the step -> row maps: every lane has read them
+  // the check iterations' T(z) of the lane's columns / rows
+  auto xpi = [&](int v, int s) -> double& { return XP[(v * S + s) * B + tid]; };
+  auto ypi = [&](int r, int s) -> double& { return YP[(r * S + s) * B + tid]; };
   if (tid < kJMax) XT[tid] = 0.0;
   if (tid == 0) XE[B] = YS[B] = 0.0;
   XE[tid] = YS[tid] = 0.0;
   for (int u = tid; u < kJMax * B; u += B) TP[u] = 0.0;
 #pragma unroll
   for (int s = 0; s < S; ++s) {
-    if constexpr (LI) {  // the outputs hold the last KKT check's T(z_k): the starting point until the first one
-      if (val[s]) {
 #pragma unroll
-        for (int v = 0; v < NC; ++v) xo_g[col(s, v)] = x[s][v] * dcf(col(s, v));
-      }
+    for (int v = 0; v < NC; ++v) xpi(v, s) = x[s][v];
 #pragma unroll
-      for (int r = 0; r < NR; ++r) {
-        const int i = row_of(s, r);
-        if (i >= 0) yo_g[i] = y[s][r] * drf(i);
-      }
-    } else {
-#pragma unroll
-      for (int v = 0; v < NC; ++v) XP[(v * S + s) * B + tid] = x[s][v];
-#pragma unroll
-      for (int r = 0; r < NR; ++r) YP[(r * S + s) * B + tid] = y[s][r];
-    }
+    for (int r = 0; r < NR; ++r) ypi(r, s) = y[s][r];
   }
   __syncthreads();
 
@@ -912,20 +748,13 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
       os[3] = fma(kb[s][1], v[4], fma(kb[s][0], v[3], -rhs(s, 3)));
     }
   };
-  // per-lane partial K'y of the tau columns from the DCM rows' values vd[s] (steps summed in order).  One column
-  // (J = 1, kTauWaveSums): every wave reduces its lanes' partials itself (one DPP tree, lane 0's sum) into TP[wid],
-  // so the tau update on wave 0 adds NW values instead of reducing B partials on the iteration's critical path.
+  // per-lane partial K'y of the tau columns from the DCM rows' values vd[s] (steps summed in order)
   auto tau_parts = [&](const double (&vd)[S]) {
     if (J == 1) {
       double a = kd[0][2] * vd[0];
 #pragma unroll
       for (int s = 1; s < S; ++s) a = fma(kd[s][2], vd[s], a);
-      if constexpr (kTauWaveSums) {
-        a = wave_sum_dpp(a);
-        if (lane == 0) TP[wid] = a;
-      } else {
-        TP[tid] = a;
-      }
+      TP[tid] = a;
     } else {
       for (int j = 0; j < J; ++j) {
         double a = (jt[0] == j ? kd[0][2] : 0.0) * vd[0];
@@ -941,17 +770,9 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
     for (int s = 0; s < S; ++s) vd[s] = vr[s][1];
     tau_parts(vd);
   };
-  // the wave sums of a single tau column, in wave order (every lane reads the same slots: a broadcast)
-  auto tau_waves = [&]() {
-    double a = TP[0];
-#pragma unroll
-    for (int r = 1; r < NW; ++r) a += TP[r];
-    return a;
-  };
   // wave 0: lane j < J gets the sum over all lanes of TP[j][.] (fixed order; uniform per column)
   auto tau_kt = [&]() {
     double res = 0.0;
-    if (kTauWaveSums && J == 1) return lane == 0 ? tau_waves() : 0.0;
     for (int j = 0; j < J; ++j) {
       double a = 0.0;
 #pragma unroll
@@ -980,8 +801,6 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
 #pragma unroll
       for (int r = 0; r < NR; ++r) wr[s][r] = 0.0;
     for (int pi = 0; pi <= P; ++pi) {
-      // (DVH_BAND_PRIO) wave 0's tau reduction is this step's critical path too, up to the first barrier
-      if (DVH_BAND_PRIO && kPrioSetup && wid == 0) __builtin_amdgcn_s_setprio(DVH_BAND_PRIO);
       if (pi > 0) {
         const double ysp = YS[tid];
 #pragma unroll
@@ -1003,7 +822,6 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
       XE[tid] = vc[0][2];
       if (wid == 0 && lane < J) XT[lane] = vtau;
       __syncthreads();
-      if (DVH_BAND_PRIO && kPrioSetup && wid == 0) __builtin_amdgcn_s_setprio(0);
       const double xen = XE[tid + 1];
 #pragma unroll
       for (int s = 0; s < S; ++s) {
@@ -1056,9 +874,7 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
   // ---- box form: x' = (x - lo) / w on the ch / dis / ene columns (after the scaling, the power iteration and the
   //      warm start's weight, which all see the original variables)
   double tj[S][3];  // per-column primal steps tau / w^2 of ch / dis / ene (elec / on: in RO, over their upper bounds)
-  double* wbox = w.vbuf + W.wn;         // the columns' widths w (window workspace: read at checks, restarts, the end)
-  double cbox = 0.0;                    // c lo, the objective's constant under the change of variables
-  auto wcol = [&](int s, int v) { return val[s] ? wbox[opaque(col(s, v))] : 0.0; };
+  double cbox = 0.0;  // c lo, the objective's constant under the change of variables
   if constexpr (BOX) {
     double wb[S][NC];
     bool unb = false;
@@ -1122,15 +938,11 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
           cc[s][v] = cs;
         const double xv = wv > 0.0 ? fmin(fmax((x[s][v] - lo) / wv, 0.0), 1.0) : 0.0;
         x[s][v] = xa[s][v] = xv;
-        if constexpr (LA) XA[(v * S + s) * B + tid] = xv;
-        XP[(v * S + s) * B + tid] = xv;
-        if constexpr (!kNoWidths) {
-          if (val[s]) wbox[col(s, v)] = wv;
-        } else if (v < 3) {  // the steps tau / w^2 from the registers (box_steps below reads them back otherwise)
+        xpi(v, s) = xv;
+        if (v < 3)  // the steps tau / w^2
           tj[s][v < 3 ? v : 0] = wv > 0.0 ? uniform(eta / pw) / (wv * wv) : 0.0;
-        } else {
+        else
           ro(v - 1, s) = wv > 0.0 ? uniform(eta / pw) / (wv * wv) : 0.0;
-        }
       }
     }
     if (ilane) {
@@ -1149,60 +961,37 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
   const int chk = o.check_every > 0 ? o.check_every : 64;
   double tau = uniform(eta / pw), sigma = uniform(eta * pw);
   double sigma2n = uniform(-2.0 * sigma);  // the equality rows' fused dual step (non-check iterations)
-  double tau_bs = tau;                     // (kBoxRescale) the tau the box steps were last formed for
-  auto box_steps = [&]() {
+  double tau_bs = tau;                     // (box form) the tau the box steps were last formed for
+  // the steps for a new tau from the current ones: tau / w^2 = (tau / tau_bs) (tau_bs / w^2)
+  auto box_steps_rescale = [&]() {
     if constexpr (BOX) {
+      const double f = uniform(tau / tau_bs);
 #pragma unroll
       for (int s = 0; s < S; ++s)
 #pragma unroll
         for (int v = 0; v < NC; ++v) {
-          const double wv = wcol(s, v), st = wv > 0.0 ? tau / (wv * wv) : 0.0;
           if (v < 3)
-            tj[s][v < 3 ? v : 0] = st;
+            tj[s][v < 3 ? v : 0] *= f;
           else
-            ro(v - 1, s) = st;
+            ro(v - 1, s) *= f;
         }
-    }
-  };
-  if constexpr (!kNoWidths) box_steps();  // (kNoWidths: formed at the box set-up)
-  // (kBoxRescale) the steps for a new tau from the current ones: tau / w^2 = (tau / tau_bs) (tau_bs / w^2)
-  auto box_steps_rescale = [&]() {
-    if constexpr (BOX) {
-      if constexpr (kBoxRescale) {
-        const double f = uniform(tau / tau_bs);
-#pragma unroll
-        for (int s = 0; s < S; ++s)
-#pragma unroll
-          for (int v = 0; v < NC; ++v) {
-            if (v < 3)
-              tj[s][v < 3 ? v : 0] *= f;
-            else
-              ro(v - 1, s) *= f;
-          }
-        tau_bs = tau;
-      } else {
-        box_steps();
-      }
+      tau_bs = tau;
     }
   };
   const int kkt_every = o.kkt_every > 0 ? o.kkt_every : 1;
   int ck = chk, kk_ = kkt_every;
   KktGate gate;  // dvh_options.kkt_predict (dvh_device.h)
   int kbase = 0;
-  auto hload = [&](int k0_) {
-    const int kq = k0_ + lane;
-    if constexpr (kHalpernDiv)  // (round 6) no global load on the restart path: the IEEE quotient the table holds
-      return 1.0 / (kq + 2.0);
-    else
-      return kq < kHalpernTab ? w.hinv[kq] : 1.0 / (kq + 2.0);
-  };
+  // The Halpern weights 1 / (k + 2) of the next kWave iterations, one correctly rounded quotient per lane.  (Loaded
+  // from a table they sat on the restart path: a restart resets k to 0 and the very next iteration reads weight 0.)
+  auto hload = [&](int k0_) { return 1.0 / (k0_ + lane + 2.0); };
   double hw = hload(0);
 
   // wave 0 with one tau column: the tau reduction is interleaved with its own column work (straight-line code,
   // the partial loads are issued first); J >= 2 takes the generic per-column loop
   const bool w0 = wid == 0 && J == 1;
   double mv0, mv1, mv2, mv3;
-  double mvb0 = 0.0, mvb1 = 0.0;  // (kBoxRescale) the box columns' movements, d'^2 / step
+  double mvb0 = 0.0, mvb1 = 0.0;  // (box form) the box columns' movements, d'^2 / step
   auto tau_update = [&](double kt, double ca, double cb, auto chk_tag) __attribute__((always_inline)) {
     constexpr bool CHECK = decltype(chk_tag)::value;
     if (tlane) {
@@ -1219,27 +1008,14 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
       }
     }
   };
-  // Lean form: the check iteration's T(z_k) (scaled) goes to the window's global workspace (the lane reads back only
-  // its own entries, at the check); padding steps write nothing
-  double* xim = w.vbuf + W.wn;
-  double* yim = w.wbuf + W.wm;
+  // the last check iteration's T(z_k) (scaled), from XP / YP
   auto load_images = [&](double (&xp)[S][NC], double (&yp)[S][NR]) {
 #pragma unroll
     for (int s = 0; s < S; ++s) {
-      if constexpr (LI) {
 #pragma unroll
-        for (int v = 0; v < NC; ++v) xp[s][v] = val[s] ? xim[opaque(col(s, v))] : 0.0;
+      for (int v = 0; v < NC; ++v) xp[s][v] = xpi(v, s);
 #pragma unroll
-        for (int r = 0; r < NR; ++r) {
-          const int i = row_of(s, r);
-          yp[s][r] = i >= 0 ? yim[opaque(i)] : 0.0;
-        }
-      } else {
-#pragma unroll
-        for (int v = 0; v < NC; ++v) xp[s][v] = XP[(v * S + s) * B + tid];
-#pragma unroll
-        for (int r = 0; r < NR; ++r) yp[s][r] = YP[(r * S + s) * B + tid];
-      }
+      for (int r = 0; r < NR; ++r) yp[s][r] = ypi(r, s);
     }
   };
   // (DVH_BAND_PROBE) stamps label the segment they end; a segment is added at the NEXT stamp, so that no stamp waits
@@ -1261,7 +1037,7 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
   auto iterate = [&](auto chk_tag, auto w0_tag) __attribute__((always_inline)) {
     constexpr bool CHECK = decltype(chk_tag)::value;
     constexpr bool W0 = decltype(w0_tag)::value;
-    if constexpr (W0 && DVH_BAND_PRIO) __builtin_amdgcn_s_setprio(DVH_BAND_PRIO);
+    if constexpr (W0) __builtin_amdgcn_s_setprio(kTauWavePrio);  // until the first barrier
     pstamp(4);  // (the check code since the last iteration, or the loop entry)
     if (kin - kbase >= kWave) {
       kbase = kin;
@@ -1275,29 +1051,22 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
     // the dual update of step s's r-th row from kx (row 0, SOE, is an equality; DCM / ICE rows are >=: duals >= 0)
     auto row_step = [&](int s, int r) __attribute__((always_inline)) {
       if (!CHECK && r == 0) {  // equality row, no image needed: 2 (y - sigma Kx) - y = y - 2 sigma Kx
-        y[s][0] = fma(ca, fma(sigma2n, kx[s][0], y[s][0]), cb * ayv(s, 0));
+        y[s][0] = fma(ca, fma(sigma2n, kx[s][0], y[s][0]), cb * ya[s][0]);
         return;
       }
       double p1 = fma(-sigma, kx[s][r], y[s][r]);
       if (r > 0) p1 = vmax(p1, 0.0);
       if (CHECK) {
-        const double d = y[s][r] - p1, da = p1 - ayv(s, r);
+        const double d = y[s][r] - p1, da = p1 - ya[s][r];
         mv2 += d * d;
         mv3 += da * da;
-        if constexpr (LI) {
-          const int i = row_of(s, r);
-          if (i >= 0) yim[opaque(i)] = p1;
-        } else {
-          YP[(r * S + s) * B + tid] = p1;
-        }
+        ypi(r, s) = p1;
       }
-      y[s][r] = fma(ca, fma(2.0, p1, -y[s][r]), cb * ayv(s, r));
+      y[s][r] = fma(ca, fma(2.0, p1, -y[s][r]), cb * ya[s][r]);
     };
     {
       double ta0 = 0.0, ta1 = 0.0;
-      if constexpr (W0 && kTauWaveSums) {
-        ta0 = tau_waves();
-      } else if constexpr (W0) {  // (0 + a == a: the first partials start the two chains)
+      if constexpr (W0) {  // (0 + a == a: the first partials start the two chains)
         ta0 = TP[lane];
         if (NW > 1) ta1 = TP[kWave + lane];
 #pragma unroll
@@ -1323,28 +1092,19 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
           }
           xb[s][v] = fma(2.0, p1, -x[s][v]);
           if (CHECK) {
-            double d = x[s][v] - p1, da = p1 - axv(s, v);
-            if constexpr (BOX && kBoxRescale) {  // movements in x units: w^2 = tau_bs / step (0 for a fixed column)
+            double d = x[s][v] - p1, da = p1 - xa[s][v];
+            if constexpr (BOX) {  // movements in x units: w^2 = tau_bs / step (0 for a fixed column)
               const double st = v < 3 ? tj[s][v < 3 ? v : 0] : ro(v - 1, s);
               const double iw = st > 0.0 ? (double)__builtin_amdgcn_rcp(st) : 0.0;
               mvb0 = fma(d * d, iw, mvb0);
               mvb1 = fma(da * da, iw, mvb1);
             } else {
-              if constexpr (BOX) {  // movements in x units
-                const double wv = wcol(s, v);
-                d *= wv;
-                da *= wv;
-              }
               mv0 += d * d;
               mv1 += da * da;
             }
-            if constexpr (LI) {
-              if (val[s]) xim[opaque(col(s, v))] = p1;
-            } else {
-              XP[(v * S + s) * B + tid] = p1;
-            }
+            xpi(v, s) = p1;
           }
-          x[s][v] = fma(ca, xb[s][v], cb * axv(s, v));
+          x[s][v] = fma(ca, xb[s][v], cb * xa[s][v]);
         }
       }
       XE[tid] = xb[0][2];
@@ -1353,27 +1113,24 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
         kown_q(s, xb[s], kx[s]);
         if (s < S - 1) kfin_next(s, kx[s], xb[s < S - 1 ? s + 1 : s][2]);  // the next step is the lane's own
       }
-      if constexpr (W0 && kTauWaveSums) {
-        tau_update(ta0, ca, cb, chk_tag);
-      } else if constexpr (W0) {
+      if constexpr (W0) {
         tau_update(uniform(wave_sum_dpp(ta0 + ta1)), ca, cb, chk_tag);
       } else {
         if (wid == 0 && J > 1) tau_update(tau_kt(), ca, cb, chk_tag);
       }
     }
     pstamp(0);
-    if constexpr (!W0 && (DVH_BAND_PIN_KX > 1 || (DVH_BAND_PIN_KX == 1 && ICE))) {  // (DVH_BAND_PIN_KX) K x-bar first
+    if constexpr (!W0 && Tune::pin_kx) {  // K x-bar before the barrier: the compiler sank it into the dual half-step
 #pragma unroll
       for (int s = 0; s < S; ++s)
 #pragma unroll
         for (int r = 0; r < NR; ++r) asm volatile("" ::"v"(kx[s][r]));
     }
     lds_barrier();
-    if constexpr (W0 && DVH_BAND_PRIO) __builtin_amdgcn_s_setprio(0);
+    if constexpr (W0) __builtin_amdgcn_s_setprio(0);
     pstamp(1);
     // ---------------- dual half-step
     {
-      if constexpr (DVH_BAND_PRIO_DUAL) __builtin_amdgcn_s_setprio(DVH_BAND_PRIO_DUAL);
       // every LDS read of the half-step first (the next lane's ene, the tau columns' x-bar), before any LDS store:
       // issued together, one wait instead of one per read
       const double xen = XE[tid + 1];
@@ -1387,12 +1144,11 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
       for (int s = 0; s < S; ++s) {
         kx[s][1] = fma(kd[s][2], xtv[s], kx[s][1]);  // kfin_tau
 #pragma unroll
-        for (int r = 1; r < ((DVH_BAND_LATE_ICE && ICE && !W0) ? 2 : NR); ++r) row_step(s, r);
+        for (int r = 1; r < ((ICE && !W0) ? 2 : NR); ++r) row_step(s, r);  // (the ICE rows: see below)
       }
       if (J > 0) tau_parts_of(y);
-      if constexpr (DVH_BAND_PRIO_DUAL) __builtin_amdgcn_s_setprio(0);
 #pragma unroll
-      for (int s = (DVH_BAND_LATE_SOE && !W0) ? S - 1 : 0; s < S; ++s) row_step(s, 0);
+      for (int s = !W0 ? S - 1 : 0; s < S; ++s) row_step(s, 0);  // (the lane-local SOE rows: see below)
       YS[tid + 1] = y[S - 1][0];
       if (W0 || wid == 0) {  // init row (lane kInitLane): ene_0 = target
         if (ilane) {
@@ -1413,7 +1169,10 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
     ++it;
     ++kin;
     pstamp(2);
-    if constexpr (W0 && DVH_BAND_PIN_BLEND) {  // (see DVH_BAND_PIN_BLEND) this iteration's blends before the barrier
+    // Wave 0 finishes this iteration's Halpern blends (x = ca x-bar + cb x-anchor, and the rows') before the second
+    // barrier, where it waits for the others anyway: the compiler sank them past the barrier, to the head of wave 0's
+    // next primal half-step -- in front of the tau reduction (profiles/r06j_pin_blend.log).
+    if constexpr (W0) {
 #pragma unroll
       for (int s = 0; s < S; ++s) {
 #pragma unroll
@@ -1423,11 +1182,15 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
       }
     }
     lds_barrier();
-    if constexpr (DVH_BAND_LATE_SOE && !W0) {  // (DVH_BAND_LATE_SOE) the lane-local SOE rows, after the barrier
+    // The waves without the tau column update the SOE rows of their lanes' steps 0 .. S - 2, and the two ICE rows, after
+    // the barrier instead of before it (those duals are read only by the lane's own next primal half-step), so that they
+    // reach the barrier -- which wave 0's next tau reduction waits behind -- sooner (profiles/r06s_ab.log,
+    // r06m_late_ice.log).
+    if constexpr (!W0) {
 #pragma unroll
       for (int s = 0; s < S - 1; ++s) row_step(s, 0);
     }
-    if constexpr (DVH_BAND_LATE_ICE && ICE && !W0) {  // (DVH_BAND_LATE_ICE) the ICE rows, after the barrier
+    if constexpr (ICE && !W0) {
 #pragma unroll
       for (int s = 0; s < S; ++s)
 #pragma unroll
@@ -1457,11 +1220,10 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
     const bool last = it + chk > o.max_iters;
     bool kkt = (--kk_ == 0) || last;
     if (kkt) kk_ = kkt_every;
-    // the ICE form reduces the round-3 set (no dual-residual term in its objective gate): the extra value cost it 6 %
-    // on config 5 at unchanged iterations (register pressure of its check path; profiles/r04ab_ab_kkt_rdx.log)
-    constexpr int NRED = (ICE && DVH_KKT_RDX) ? kNRed - 1 : kNRed;
+    static_assert(kRdx == kNRed - 1, "the dual-residual term is the last reduced value");
+    constexpr int NRED = Tune::gate_rdx ? kNRed : kNRed - 1;
     double acc[NRED];
-    acc[0] = fma(tau_bs, mvb0, mv0);  // (mvb0 = mvb1 = 0 without kBoxRescale)
+    acc[0] = fma(tau_bs, mvb0, mv0);  // (mvb0 = mvb1 = 0 in the plain form)
     acc[1] = fma(tau_bs, mvb1, mv1);
     acc[2] = mv2;
     acc[3] = mv3;
@@ -1482,12 +1244,12 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
       }
     }
     if (kkt) {
-      // (kkt_prefetch) the single-precision factors of the lane's columns and rows, loaded together first: one wait
+      // (Tune::kkt_prefetch) the single-precision factors of the lane's columns and rows, loaded together first: one wait
       // for all of them, behind the image reads and the barrier below
       // (branch-free: a padding step / absent row loads the window's first entry and discards it; the indices are
       // formed here from an opaque thread index, so that they are not hoisted out of the loop and held)
       float fcl[S][NC], frl[S][NR], fspl = 1.0f;
-      if constexpr (kkt_prefetch<ICE>()) {
+      if constexpr (Tune::kkt_prefetch) {
         const int to = S * opaque(tid);
         const float* fcw = w.fc + W.wn;
         const float* frw = w.fr + W.wm;
@@ -1521,23 +1283,24 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
       if (J > 0) tau_parts_of(yp);
       lds_barrier();
       auto col_kkt = [&](int j, double kt, double cj, double loj, double hij, double xj, float fpre) {
-        const float fd = kkt_prefetch<ICE>() ? fpre : w.fc[W.wn + opaque(j)];
-        if constexpr (NRED > kRdx && DVH_KKT_RDX) {
-          const ColKktX r = col_kkt_fn_x<kkt_inline<ICE>()>(kt, cj, loj, hij, xj, fd);
+        const float fd = Tune::kkt_prefetch ? fpre : w.fc[W.wn + opaque(j)];
+        static_assert(Tune::gate_rdx == Tune::kkt_inline, "col_kkt_x_i is inlined only, col_kkt_o out of line only");
+        if constexpr (Tune::gate_rdx) {
+          const ColKktX r = col_kkt_x_i(kt, cj, loj, hij, xj, fd);
           acc[5] += r.rd2;
           acc[6] += r.cx;
           acc[8] += r.bt;
           acc[kRdx] += r.rdx;
         } else {
-          const ColKkt r = col_kkt_fn<kkt_inline<ICE>()>(kt, cj, loj, hij, xj, fd);
+          const ColKkt r = col_kkt_o(kt, cj, loj, hij, xj, fd);
           acc[5] += r.rd2;
           acc[6] += r.cx;
           acc[8] += r.bt;
         }
       };
       auto row_kkt = [&](int i, double kv, double qi, double yi, bool ge, float fpre) {
-        const float fd = kkt_prefetch<ICE>() ? fpre : w.fr[W.wm + opaque(i)];
-        const RowKkt r = row_kkt_fn<kkt_inline<ICE>()>(kv, qi, yi, fd, ge);
+        const float fd = Tune::kkt_prefetch ? fpre : w.fr[W.wm + opaque(i)];
+        const RowKkt r = row_kkt_fn<Tune::kkt_inline>(kv, qi, yi, fd, ge);
         acc[4] += r.rp2;
         acc[7] += qi * yi;
         acc[9] += r.y2;
@@ -1572,20 +1335,6 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
         if (val[s]) row_kkt(t + 1, kv[0], qv(s, 0), yp[s][0], false, frl[s][0]);
         const int dr_ = DRL[s * B + tid];
         if (dr_ >= 0) row_kkt(dr_, kv[1], qv(s, 1), yp[s][1], true, frl[s][1]);
-        if constexpr (LI) {  // this check's T(z_k), unscaled, as the outputs
-          if (val[s]) {
-#pragma unroll
-            for (int v = 0; v < NC; ++v) {
-              const int j = opaque(col(s, v));
-              xo_g[j] = xp[s][v] * dcf(j);
-            }
-          }
-#pragma unroll
-          for (int r = 0; r < NR; ++r) {
-            const int i = row_of(s, r);
-            if (i >= 0) yo_g[opaque(i)] = yp[s][r] * drf(opaque(i));
-          }
-        }
         if (ICE && val[s]) {
           row_kkt(ra[s], kv[2], rhs(s, 2), yp[s][2], true, frl[s][NR > 2 ? 2 : 0]);
           row_kkt(rb[s], kv[3], rhs(s, 3), yp[s][3], true, frl[s][NR > 3 ? 3 : 0]);
@@ -1622,7 +1371,7 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
         fin[2] = dres;
         fin[3] = gap;
       }
-      if (kkt_done(o, pres, dres, gap, pobj, dobj, acc[4], acc[9], (NRED > kRdx && DVH_KKT_RDX) ? acc[kRdx] : 0.0)) {
+      if (kkt_done(o, pres, dres, gap, pobj, dobj, acc[4], acc[9], Tune::gate_rdx ? acc[kRdx] : 0.0)) {
         status = kOptimal;
         break;
       }
@@ -1651,19 +1400,11 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
       for (int s = 0; s < S; ++s) {
 #pragma unroll
         for (int v = 0; v < NC; ++v) {
-          x[s][v] = xp[s][v];
-          if constexpr (LA)
-            XA[(v * S + s) * B + tid] = x[s][v];
-          else
-            xa[s][v] = x[s][v];
+          x[s][v] = xa[s][v] = xp[s][v];
         }
 #pragma unroll
         for (int rr = 0; rr < NR; ++rr) {
-          y[s][rr] = yp[s][rr];
-          if constexpr (LA)
-            YA[(rr * S + s) * B + tid] = y[s][rr];
-          else
-            ya[s][rr] = y[s][rr];
+          y[s][rr] = ya[s][rr] = yp[s][rr];
         }
       }
       if (ilane) sp[0] = sp[1] = sp[2];
@@ -1685,34 +1426,29 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
     // (a restart check that neither restarts nor checks KKT rewrote no shared value: the next iteration reads what the
     // check iteration wrote before its barriers, and `red` is next written two barriers later -- no barrier here)
   }
-  // outputs: the last check's T(z_k), unscaled (the lean form wrote them at that check)
+  // outputs: the last check's T(z_k), unscaled
 #pragma unroll
   for (int s = 0; s < S; ++s) {
-    if (LI || !val[s]) continue;
+    if (!val[s]) continue;
     const int t = t0 + s;
 #pragma unroll
     for (int v = 0; v < NC; ++v) {
       const int j = col(s, v);
       if constexpr (BOX) {  // x = lo + w x' (clipped to the box against the rounding), then unscaled
         const double d = dcf(j), lo = lraw[j] / d, hv = uraw[j] / d;
-        double wv;
-        if constexpr (kNoWidths) {  // the set-up's width, by the set-up's operations
-          wv = hv - (v == 2 ? lo : 0.0);
-          if (!(wv >= 0x1p-500)) wv = 0.0;
-        } else {
-          wv = wbox[j];
-        }
-        xo_g[j] = fmin(fmax(fma(wv, XP[(v * S + s) * B + tid], lo), lo), hv) * d;
+        double wv = hv - (v == 2 ? lo : 0.0);  // the set-up's width, by the set-up's operations
+        if (!(wv >= 0x1p-500)) wv = 0.0;
+        xo_g[j] = fmin(fmax(fma(wv, xpi(v, s), lo), lo), hv) * d;
       } else {
-        xo_g[j] = XP[(v * S + s) * B + tid] * dcf(j);
+        xo_g[j] = xpi(v, s) * dcf(j);
       }
     }
-    yo_g[t + 1] = YP[s * B + tid] * drf(t + 1);
+    yo_g[t + 1] = ypi(0, s) * drf(t + 1);
     const int dr_ = DRL[s * B + tid];
-    if (dr_ >= 0) yo_g[dr_] = YP[(S + s) * B + tid] * drf(dr_);
+    if (dr_ >= 0) yo_g[dr_] = ypi(1, s) * drf(dr_);
     if (ICE) {
-      yo_g[ra[s]] = YP[(2 * S + s) * B + tid] * drf(ra[s]);
-      yo_g[rb[s]] = YP[(3 * S + s) * B + tid] * drf(rb[s]);
+      yo_g[ra[s]] = ypi(2, s) * drf(ra[s]);
+      yo_g[rb[s]] = ypi(3, s) * drf(rb[s]);
     }
   }
   if (tlane) xo_g[3 * T + lane] = sp[5] * dcf(3 * T + lane);
@@ -1735,21 +1471,14 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
   }
 }
 
-// Persistent form (PERSIST; the three-step battery form): the grid is the device's resident workgroup slots (two per CU),
-// and each workgroup takes the next window from an atomic counter until the list is exhausted, so a slot freed by a
-// short window takes the next one at once.  One workgroup per window left the slots to the hardware dispatcher,
+// Persistent form (PERSIST: the three-step battery form and the ICE form): the grid is the device's resident workgroup
+// slots, and each workgroup takes the next window from an atomic counter until the list is exhausted, so a slot freed
+// by a short window takes the next one at once.  One workgroup per window left the slots to the hardware dispatcher,
 // which deals workgroups in order round-robin over the XCDs: with durations that vary window to window (warm
-// iterations 200 .. 10,000) the in-order dispatch leaves slots idle.  Measured: the bench's windows ran 7-8 % faster
-// when launched sorted by their own iteration counts (either direction, profiles/r04r_ab_launch_order.log), a
-// synthetic kernel of random durations lost 20 % to the sorted order (scripts/probe_dispatch.hip,
-// profiles/r04t_probe_dispatch.log: 33.5 vs 28.2 ms, persistent 29.9), and the persistent band kernel runs the
-// bench's PDHG in 467 vs 478 ms (profiles/r04u_ab_band_queue.log).  The persistent instantiations (the three-step
-// battery form and the ICE form) are compiled in dvh_band_persist.hip without machine-level loop-invariant code motion:
-// built with it, the window setup's invariants were hoisted out of the loop over windows and spilled (12.6 % slower per
-// iteration, and the ICE form 61k vs 91k windows/s on config 5).  Now the battery form's PDHG runs 441 vs 459 ms and
-// config 5 112.7k vs 95.6k windows/s (profiles/r04al_band_persist_nolicm.log, r04an_ab_ice_queue.log); the one-step
-// battery form stays one workgroup per window.  Every workgroup leaves once the counter passes the list (the counter
-// zeroed on the stream before the launch).
+// iterations 200 .. 10,000) the in-order dispatch leaves slots idle (profiles/r04r_ab_launch_order.log,
+// r04t_probe_dispatch.log, r04u_ab_band_queue.log, r04an_ab_ice_queue.log).  Every workgroup leaves once the counter
+// passes the list (the counter zeroed on the stream before the launch).  The one-step battery form stays one workgroup
+// per window.
 struct BandArgs {
   Batch b;
   Work w;
@@ -1759,11 +1488,11 @@ struct BandArgs {
   int count;            // windows to solve (list entries, or the chunk's)
   int32_t* queue;       // work-queue counter (PERSIST), zeroed before the launch
 };
-template <int B, int S, bool ICE, int LF, int WPS, bool GATE, bool BOX, bool PERSIST>
+template <int B, int S, bool ICE, bool LC, int WPS, bool GATE, bool BOX, bool PERSIST>
 __global__ __launch_bounds__(B, WPS) void pdhg_band_kernel(const BandArgs args) {
   if constexpr (!PERSIST) {
     const int i = blockIdx.x;
-    band_window<B, S, ICE, LF, WPS, GATE, BOX>(args.b, args.w, args.ch, args.o,
+    band_window<B, S, ICE, LC, WPS, GATE, BOX>(args.b, args.w, args.ch, args.o,
                                                args.list ? args.list[i] : args.ch.first + i, threadIdx.x);
   } else {
     __shared__ int32_t next;
@@ -1791,24 +1520,18 @@ __global__ __launch_bounds__(B, WPS) void pdhg_band_kernel(const BandArgs args) 
 #if defined(__HIP_DEVICE_COMPILE__)
       asm volatile("" : "+v"(tid));  // (likewise what the window derives from its thread index)
 #endif
-      band_window<B, S, ICE, LF, WPS, GATE, BOX>(args.b, args.w, args.ch, args.o,
+      band_window<B, S, ICE, LC, WPS, GATE, BOX>(args.b, args.w, args.ch, args.o,
                                                  args.list ? args.list[i] : args.ch.first + i, tid);
     }
   }
 }
 
-#ifndef DVH_BANDI_LF
-#define DVH_BANDI_LF 0
-#endif
-#ifndef DVH_BAND3_LF
-#define DVH_BAND3_LF kLfCosts
-#endif
-template <int B, int S, bool ICE, int LF, int WPS, bool GATE, bool BOX, bool PERSIST>
+template <int B, int S, bool ICE, bool LC, int WPS, bool GATE, bool BOX, bool PERSIST>
 hipError_t launch_band_one_q(const Batch& b, const Work& w, const Chunk& ch, const Opts& o, hipStream_t s,
                              const int32_t* list, int nlist, int* variant_out) {
   static_assert(B * S == kBandSteps, "every form covers T <= kBandSteps");
-  const size_t lds = band_lds_bytes(B, S, ICE, LF);
-  auto kern = pdhg_band_kernel<B, S, ICE, LF, WPS, GATE, BOX, PERSIST>;
+  const size_t lds = band_lds_bytes(B, S, ICE, LC);
+  auto kern = pdhg_band_kernel<B, S, ICE, LC, WPS, GATE, BOX, PERSIST>;
   hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
   if (getenv("DVH_BAND_OCC")) {  // residency diagnostics (A/B helper)
@@ -1820,7 +1543,7 @@ hipError_t launch_band_one_q(const Batch& b, const Work& w, const Chunk& ch, con
     hipFuncAttributes fa;
     hipFuncGetAttributes(&fa, (const void*)kern);
     fprintf(stderr, "band<%d,%d,%d,%d,gate %d,box %d,persist %d>: lds %zu B, blocks/CU %d, lds/CU %zu, regs %d, local %zu\n",
-            B, S, (int)ICE, LF, (int)GATE, (int)BOX, (int)PERSIST, lds, nb, (size_t)pr.maxSharedMemoryPerMultiProcessor,
+            B, S, (int)ICE, (int)LC, (int)GATE, (int)BOX, (int)PERSIST, lds, nb, (size_t)pr.maxSharedMemoryPerMultiProcessor,
             fa.numRegs, (size_t)fa.localSizeBytes);
   }
   const int count = list ? nlist : ch.count;
@@ -1848,42 +1571,37 @@ hipError_t launch_band_one_q(const Batch& b, const Work& w, const Chunk& ch, con
   if (variant_out) *variant_out = 9000000 + 1000 * (S - 1) + (ICE ? 100 : 0) + B / kWave;
   return hipGetLastError();
 }
-template <int B, int S, bool ICE, int LF, int WPS, bool GATE, bool BOX>
+template <int B, int S, bool ICE, bool LC, int WPS, bool GATE, bool BOX>
 hipError_t launch_band_one_g(const Batch& b, const Work& w, const Chunk& ch, const Opts& o, hipStream_t s,
                              const int32_t* list, int nlist, int* variant_out) {
   if constexpr (S == 3 && !ICE) {  // the persistent form (DVH_BAND_QUEUE=0: one workgroup per window, A/B)
-    static_assert(B == kBandSteps / 3 && LF == DVH_BAND3_LF && WPS == 2, "dvh_band_persist.hip instantiates this form");
+    static_assert(B == kBandSteps / 3 && LC && WPS == 2, "dvh_band_persist.hip instantiates this form");
     const char* q = getenv("DVH_BAND_QUEUE");
     if (!(q && atoi(q) == 0)) return launch_band_persist(GATE, BOX, b, w, ch, o, s, list, nlist, variant_out);
   }
   if constexpr (ICE) {  // the ICE form's persistent grid (DVH_BAND_QUEUE=0 or DVH_BAND_QUEUE_ICE=0: off, A/B)
-    static_assert(B == kBandSteps && S == 1 && LF == DVH_BANDI_LF && WPS == 3, "dvh_band_persist_ice.hip instantiates this form");
+    static_assert(B == kBandSteps && S == 1 && !LC && WPS == 3, "dvh_band_persist_ice.hip instantiates this form");
     const char* q = getenv("DVH_BAND_QUEUE");
     const char* qi = getenv("DVH_BAND_QUEUE_ICE");
     if (!(q && atoi(q) == 0) && !(qi && atoi(qi) == 0))
       return launch_band_persist_ice(GATE, BOX, b, w, ch, o, s, list, nlist, variant_out);
   }
-  return launch_band_one_q<B, S, ICE, LF, WPS, GATE, BOX, false>(b, w, ch, o, s, list, nlist, variant_out);
+  return launch_band_one_q<B, S, ICE, LC, WPS, GATE, BOX, false>(b, w, ch, o, s, list, nlist, variant_out);
 }
-template <int B, int S, bool ICE, int LF, int WPS, bool BOX = false>
+template <int B, int S, bool ICE, bool LC, int WPS, bool BOX = false>
 hipError_t launch_band_one(const Batch& b, const Work& w, const Chunk& ch, const Opts& o, hipStream_t s,
                            const int32_t* list, int nlist, int* variant_out) {
   if (o.kkt_predict > 0)
-    return launch_band_one_g<B, S, ICE, LF, WPS, true, BOX>(b, w, ch, o, s, list, nlist, variant_out);
-  return launch_band_one_g<B, S, ICE, LF, WPS, false, BOX>(b, w, ch, o, s, list, nlist, variant_out);
+    return launch_band_one_g<B, S, ICE, LC, WPS, true, BOX>(b, w, ch, o, s, list, nlist, variant_out);
+  return launch_band_one_g<B, S, ICE, LC, WPS, false, BOX>(b, w, ch, o, s, list, nlist, variant_out);
 }
 
 }  // namespace
 
-// Forms of the battery (non-ICE) band kernel.  form 3 (default): 256 threads = one wave per SIMD, three steps per
-// lane, <= 256 VGPRs = 2 waves per SIMD, so two windows share every CU (a 384-thread, two-step form with 3 waves
-// per SIMD was measured to run one window per CU in practice: its 6 waves cannot be placed 3 / 3 / 3 / 3); the
-// costs / right-hand sides in LDS keep its three steps' state in 256 VGPRs without spills in the iteration, and the
-// setup-only ints share the check images' LDS so that two windows fit one CU's LDS (74 KB each).  Measured
-// (profiles/r02x_band_forms.log): 0.51 vs 0.69 us per window-iteration per CU; with the images in the global
-// workspace (kLfImages) 5 % slower and 10x the HBM writes, with the anchors in LDS too (kLfAnchors) 8 % slower.
-// form 1: 768 threads, one step per lane, 12 waves, one window per CU (A/B, dvh_set_kernel_path 3).  The LP-relaxed
-// ICE windows keep the one-step form (twice the per-step state).
+// The form for a batch (the file header lists them): form 3, the default, is the three-step battery form, form 1 the
+// one-step one (dvh_set_kernel_path 3; dvh_api.cpp takes it for batches of at most one window per CU); the LP-relaxed
+// ICE windows have the one-step ICE form only.  (A 384-thread, two-step form with 3 waves per SIMD ran one window per
+// CU in practice: its 6 waves cannot be placed 3 / 3 / 3 / 3; profiles/r02x_band_forms.log.)
 #if DVH_BAND_PERSIST_TU == 1
 // The persistent forms (three-step battery: dvh_band_persist.hip, DVH_BAND_PERSIST_TU 1; ICE: dvh_band_persist_ice.hip, 2),
 // each this file in a translation unit of its own, compiled without
@@ -1895,36 +1613,36 @@ hipError_t launch_band_persist(bool gate, bool box, const Batch& b, const Work& 
                                hipStream_t s, const int32_t* list, int nlist, int* variant_out) {
   constexpr int B = kBandSteps / 3;
   if (gate) {
-    if (box) return launch_band_one_q<B, 3, false, DVH_BAND3_LF, 2, true, true, true>(b, w, ch, o, s, list, nlist, variant_out);
-    return launch_band_one_q<B, 3, false, DVH_BAND3_LF, 2, true, false, true>(b, w, ch, o, s, list, nlist, variant_out);
+    if (box) return launch_band_one_q<B, 3, false, true, 2, true, true, true>(b, w, ch, o, s, list, nlist, variant_out);
+    return launch_band_one_q<B, 3, false, true, 2, true, false, true>(b, w, ch, o, s, list, nlist, variant_out);
   }
-  if (box) return launch_band_one_q<B, 3, false, DVH_BAND3_LF, 2, false, true, true>(b, w, ch, o, s, list, nlist, variant_out);
-  return launch_band_one_q<B, 3, false, DVH_BAND3_LF, 2, false, false, true>(b, w, ch, o, s, list, nlist, variant_out);
+  if (box) return launch_band_one_q<B, 3, false, true, 2, false, true, true>(b, w, ch, o, s, list, nlist, variant_out);
+  return launch_band_one_q<B, 3, false, true, 2, false, false, true>(b, w, ch, o, s, list, nlist, variant_out);
 }
 #elif DVH_BAND_PERSIST_TU == 2
 hipError_t launch_band_persist_ice(bool gate, bool box, const Batch& b, const Work& w, const Chunk& ch, const Opts& o,
                                    hipStream_t s, const int32_t* list, int nlist, int* variant_out) {
   constexpr int B = kBandSteps;
   if (gate) {
-    if (box) return launch_band_one_q<B, 1, true, DVH_BANDI_LF, 3, true, true, true>(b, w, ch, o, s, list, nlist, variant_out);
-    return launch_band_one_q<B, 1, true, DVH_BANDI_LF, 3, true, false, true>(b, w, ch, o, s, list, nlist, variant_out);
+    if (box) return launch_band_one_q<B, 1, true, false, 3, true, true, true>(b, w, ch, o, s, list, nlist, variant_out);
+    return launch_band_one_q<B, 1, true, false, 3, true, false, true>(b, w, ch, o, s, list, nlist, variant_out);
   }
-  if (box) return launch_band_one_q<B, 1, true, DVH_BANDI_LF, 3, false, true, true>(b, w, ch, o, s, list, nlist, variant_out);
-  return launch_band_one_q<B, 1, true, DVH_BANDI_LF, 3, false, false, true>(b, w, ch, o, s, list, nlist, variant_out);
+  if (box) return launch_band_one_q<B, 1, true, false, 3, false, true, true>(b, w, ch, o, s, list, nlist, variant_out);
+  return launch_band_one_q<B, 1, true, false, 3, false, false, true>(b, w, ch, o, s, list, nlist, variant_out);
 }
 #else
 hipError_t launch_pdhg_band(const Batch& b, const Work& w, const Chunk& ch, const Opts& o, hipStream_t s, bool ice,
                             int form, bool box, const int32_t* list, int nlist, int* variant_out) {
   if (ice) {
-    if (box) return launch_band_one<kBandSteps, 1, true, DVH_BANDI_LF, 3, true>(b, w, ch, o, s, list, nlist, variant_out);
-    return launch_band_one<kBandSteps, 1, true, DVH_BANDI_LF, 3>(b, w, ch, o, s, list, nlist, variant_out);
+    if (box) return launch_band_one<kBandSteps, 1, true, false, 3, true>(b, w, ch, o, s, list, nlist, variant_out);
+    return launch_band_one<kBandSteps, 1, true, false, 3>(b, w, ch, o, s, list, nlist, variant_out);
   }
   if (form == 1) {
-    if (box) return launch_band_one<kBandSteps, 1, false, 0, 3, true>(b, w, ch, o, s, list, nlist, variant_out);
-    return launch_band_one<kBandSteps, 1, false, 0, 3>(b, w, ch, o, s, list, nlist, variant_out);
+    if (box) return launch_band_one<kBandSteps, 1, false, false, 3, true>(b, w, ch, o, s, list, nlist, variant_out);
+    return launch_band_one<kBandSteps, 1, false, false, 3>(b, w, ch, o, s, list, nlist, variant_out);
   }
-  if (box) return launch_band_one<kBandSteps / 3, 3, false, DVH_BAND3_LF, 2, true>(b, w, ch, o, s, list, nlist, variant_out);
-  return launch_band_one<kBandSteps / 3, 3, false, DVH_BAND3_LF, 2>(b, w, ch, o, s, list, nlist, variant_out);
+  if (box) return launch_band_one<kBandSteps / 3, 3, false, true, 2, true>(b, w, ch, o, s, list, nlist, variant_out);
+  return launch_band_one<kBandSteps / 3, 3, false, true, 2>(b, w, ch, o, s, list, nlist, variant_out);
 }
 #endif
 

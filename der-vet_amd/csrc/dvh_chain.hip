@@ -49,7 +49,7 @@ constexpr int kCB = kChainB;  // threads (and maximum steps) per segment
 #endif
 constexpr int kTauWave = DVH_CHAIN_TAU_WAVE;  // the wave holding the tau slots (wave 0 holds the init / ghost row)
 // DVH_CHAIN_PRIO (round 6, A/B, off): s_setprio for the waves whose primal half-step ends in a hand-off (as the band
-// kernel's wave 0, DVH_BAND_PRIO), until they have published.  DVH_CHAIN_KKT_PREFETCH (A/B, off): a KKT check's factor
+// kernel's wave 0, kTauWavePrio), until they have published.  DVH_CHAIN_KKT_PREFETCH (A/B, off): a KKT check's factor
 // loads issued together at the top of the check (as the band kernel's).  Measured and not kept
 // (profiles/r06f_chain_ab.log): config 3 DCM + PV 6.6 / 6.6 windows/s with prefetch / + priority against 6.8 without
 // (the prefetched doubles raise the spills 25 -> 36 VGPRs around the out-of-line KKT helpers), medium annual 1,526 /
@@ -1371,7 +1371,7 @@ __global__ __launch_bounds__(kCB, 3) void pdhg_chain_kernel(const Batch b, const
           acc[5] += r.rd2;
           acc[6] += r.cx;
           acc[8] += r.bt;
-          if (DVH_KKT_RDX) acc[kRdx] += r.rdx;
+          acc[kRdx] += r.rdx;
         };
         auto row_kkt = [&](int i, double kv, double qi, double yi, bool ge, double dpre) {
           const RowKktC r = row_kkt_c(kv, qi, yi, DVH_CHAIN_KKT_PREFETCH ? dpre : drv[opaque(i)], ge);
@@ -1411,7 +1411,7 @@ __global__ __launch_bounds__(kCB, 3) void pdhg_chain_kernel(const Batch b, const
         fin[1] = pres;
         fin[2] = dres;
         fin[3] = gap;
-        if (kkt_done(o, pres, dres, gap, pobj, dobj, acc[4], acc[9], DVH_KKT_RDX ? acc[kRdx] : 0.0)) {
+        if (kkt_done(o, pres, dres, gap, pobj, dobj, acc[4], acc[9], acc[kRdx])) {
           status = kOptimal;
           break;
         }

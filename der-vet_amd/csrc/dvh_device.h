@@ -9,11 +9,8 @@
 namespace dvh {
 namespace {
 
-#ifndef DVH_KKT_RDX
-#define DVH_KKT_RDX 1  // the objective gate's dual-residual term (kkt_done); 0: the round-3 gate (A/B builds)
-#endif
-constexpr int kNRed = 10 + DVH_KKT_RDX;  // values reduced by a termination (KKT) check ([10]: sum_j |r_d,j| |x_j|)
-constexpr int kRdx = DVH_KKT_RDX ? 10 : 0;  // its slot (an unused 0 slot without it)
+constexpr int kNRed = 11;  // values reduced by a termination (KKT) check
+constexpr int kRdx = 10;   // the slot of sum_j |r_d,j| |x_j|, the objective gate's dual-residual term (kkt_done)
 __host__ __device__ constexpr size_t align16(size_t x) { return (x + 15) & ~size_t(15); }
 
 constexpr int kOptimal = 0, kIterLimit = 3, kNumerical = 4;
@@ -68,13 +65,8 @@ __device__ __forceinline__ double row_sum16(double v) {
 }
 
 // Primal-weight update w <- exp(theta log(ratio) + (1 - theta) log(w)) (PDLP smoothing).  theta = 1 and
-// theta = 0.5 have closed forms.  [r5] The general case is inlined too (DVH_PW_INLINE, default 1): as a call it
-// bound the kernels' live registers to the call ABI at its call site -- inlined, the market days run 11.1 / 14.8 ms
-// (market options / defaults) instead of 11.4 / 15.7 and config 3 168 instead of 174 ms
-// (profiles/r05v_pw_inline.log).
-#ifndef DVH_PW_INLINE
-#define DVH_PW_INLINE 1
-#endif
+// theta = 0.5 have closed forms.  The general case is inlined too: as a call it bound the kernels' live registers to
+// the call ABI at its call site (profiles/r05v_pw_inline.log).
 __device__ __forceinline__ double pw_update_general_i(double ratio, double w, double theta) {
   return exp(theta * log(ratio) + (1.0 - theta) * log(w));
 }
@@ -86,7 +78,7 @@ template <bool INL = true>
 __device__ __forceinline__ double pw_update(double ratio, double w, double theta) {
   if (theta == 1.0) return ratio;
   if (theta == 0.5) return sqrt(ratio * w);
-  if constexpr (INL && DVH_PW_INLINE) return pw_update_general_i(ratio, w, theta);
+  if constexpr (INL) return pw_update_general_i(ratio, w, theta);
   else return pw_update_general_o(ratio, w, theta);
 }
 
@@ -168,8 +160,8 @@ __device__ __forceinline__ void block_sum1(double (&v)[NV], double* red) {
 // rdx: sum_j |r_d,j| |x_j|, what the dual objective can overstate the optimum by (p* >= dobj - sum_j
 // |r_d,j| |x*_j|, with x in place of x*): a window whose dual residual sits on a large column (the demand charge's tau)
 // otherwise stopped with its objective 1.6e-6 off (profiles/r04y_certify.json).  Every kernel applies it except the
-// band ICE form (NRED = kNRed - 1 in dvh_band.hip: the term cost 6 % on config 5 through its check path's registers,
-// DESIGN.md section 4), whose windows keep the round-3 test; both restatements (oracle/pdlp_ref.py,
+// band ICE form (BandTune<true>::gate_rdx in dvh_band.hip: the term cost 6 % on config 5 through its check path's
+// registers), whose windows keep the round-3 test; both restatements (oracle/pdlp_ref.py,
 // oracle/cpu_pdhg.cpp) apply it to every window, so an ICE window can end one check later there than on the GPU.
 __device__ __forceinline__ bool kkt_done(const Opts& o, double pres, double dres, double gap, double pobj,
                                          double dobj, double rp2, double y2, double rdx = 0.0) {

@@ -706,7 +706,7 @@ __global__ __launch_bounds__(B) void pdhg_kernel(const Batch b, const Work w, co
       acc[5] += rd * rd;
       acc[6] += cj * xj;
       acc[8] += (fl ? loj * d * fmax(lam, 0.0) : 0.0) + (fh ? hij * d * fmin(lam, 0.0) : 0.0);
-      if (DVH_KKT_RDX) acc[kRdx] += fabs(rd) * fabs(xj * d);
+      acc[kRdx] += fabs(rd) * fabs(xj * d);
     };
     auto row_kkt = [&](int i, double kx, double qi, double yi) {
       const double d = drv[i];
@@ -756,7 +756,7 @@ __global__ __launch_bounds__(B) void pdhg_kernel(const Batch b, const Work w, co
       fin[1] = pres;
       fin[2] = dres;
       fin[3] = gap;
-      if (kkt_done(o, pres, dres, gap, pobj, dobj, acc[4], acc[9], DVH_KKT_RDX ? acc[kRdx] : 0.0)) {
+      if (kkt_done(o, pres, dres, gap, pobj, dobj, acc[4], acc[9], acc[kRdx])) {
         status = kOptimal;
         break;
       }
@@ -1493,7 +1493,7 @@ __global__ __launch_bounds__(B) __attribute__((amdgpu_waves_per_eu(WPE))) void p
         acc[5] += rd * rd;
         acc[6] += cj * xj;
         acc[8] += (fl ? loj * d * fmax(lam, 0.0) : 0.0) + (fh ? hij * d * fmin(lam, 0.0) : 0.0);
-        if (DVH_KKT_RDX) acc[kRdx] += fabs(rd) * fabs(xj * d);
+        acc[kRdx] += fabs(rd) * fabs(xj * d);
       };
       auto row_kkt = [&](int i, double kv, double qi, double yi2) {
         const double d = drv[opaque(i)];
@@ -1555,7 +1555,7 @@ __global__ __launch_bounds__(B) __attribute__((amdgpu_waves_per_eu(WPE))) void p
         fin[2] = dres;
         fin[3] = gap;
       }
-      if (kkt_done(o, pres, dres, gap, pobj, dobj, acc[4], acc[9], DVH_KKT_RDX ? acc[kRdx] : 0.0)) {
+      if (kkt_done(o, pres, dres, gap, pobj, dobj, acc[4], acc[9], acc[kRdx])) {
         status = kOptimal;
         break;
       }
@@ -1670,13 +1670,9 @@ hipError_t launch_ell_one(const Batch& b, const Work& w, const Chunk& ch, const 
 // KR variants keep K / K^T in VGPRs: 768-thread workgroups (12 waves, <= 168 VGPRs) cover the monthly
 // battery + DCM window (n <= 2304, m <= 1536) with three waves per SIMD; larger windows keep the values in
 // LDS with 512 threads.
-#ifndef DVH_KR768
-#define DVH_KR768 -1
-#endif
 // K and K^T in VGPRs for the narrow <2,4> slices (the monthly battery + DCM window: measured 1.40 vs 1.59
 // us per window-iteration per CU against K^T in LDS).
-template <int WX, int WY>
-constexpr int kr768() { return DVH_KR768 >= 0 ? DVH_KR768 : 3; }
+constexpr int kKr768 = 3;
 template <int WX, int WY>
 hipError_t ell_dispatch_xy(int max_n, int max_m, const Batch& b, const Work& w, const Chunk& ch, const Opts& o,
                            hipStream_t s, int* variant_out, const int32_t* list, int nlist) {
@@ -1692,13 +1688,11 @@ hipError_t ell_dispatch_xy(int max_n, int max_m, const Batch& b, const Work& w, 
   }
   DVH_CASE(512, 1, 1, 3)
   DVH_CASE(512, 2, 2, 3)
-#ifndef DVH_NO768
   // <2,4> slices only: the <4,8> form (K in VGPRs) spilled 144-165 VGPRs at the 768-thread budget, and no measured
   // workload reached it (POI windows of 1,921 columns refuse the ELL shape, profiles/r05y_poi_paths.log)
   if constexpr (WX <= 2 && WY <= 4) {
-    DVH_CASE(768, 3, 2, (kr768<WX, WY>()))
+    DVH_CASE(768, 3, 2, kKr768)
   }
-#endif
   DVH_CASE(512, 5, 3, 0)
   // (<512,6,4> of the <2,4> slices dropped: 61-72 spilled VGPRs and no measured workload -- its windows, n in
   // (2560, 3072], take the generic kernel)

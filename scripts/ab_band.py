@@ -1,4 +1,4 @@
-"""A/B of libdervet_hip builds (scripts/build_variants.sh) on config-4 windows: per-iteration cost at a fixed
+"""A/B of libdervet_hip builds (dervet_hip.build.build_variant) on config-4 windows: per-iteration cost at a fixed
 iteration count (no convergence) and a converged cold solve (time, mean iterations, objectives vs the first build).
 
 Usage: python scripts/ab_band.py <scenarios> <fixed_iters> <lib.so> [<lib.so> ...]

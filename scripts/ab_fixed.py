@@ -1,5 +1,5 @@
 """Per-iteration cost of library builds at a FIXED iteration count (no convergence; dev helper for A/B of
-kernel variants built with scripts/build_variants.sh, including deliberately incomplete ablations).
+kernel variants built with dervet_hip.build.build_variant, including deliberately incomplete ablations).
 
 Usage: python scripts/ab_fixed.py <scenarios> <iters> <lib.so> [<lib.so> ...]
        DVH_AB_OPTS='{"label": {"check_every": 16, "kkt_every": 4}, ...}' overrides the option sets.

@@ -1,4 +1,4 @@
-"""A/B of library builds on a config-4 sample (dev helper; variants from scripts/build_variants.sh).
+"""A/B of library builds on a config-4 sample (dev helper; variants from dervet_hip.build.build_variant).
 
 Usage: python scripts/ab_variants.py <scenarios> <lib.so> [<lib.so> ...]
 Each library runs in its own subprocess (one ctypes load per process); prints PDHG kernel time, iteration

@@ -5,7 +5,7 @@ import numpy as np, torch
 from dervet_hip import BatchSolver, _lib
 from dervet_hip.lp import scenarios, builder
 S = int(sys.argv[1]) if len(sys.argv) > 1 else 256
-if len(sys.argv) > 2:  # A/B: load an alternative build (scripts/build_variants.sh)
+if len(sys.argv) > 2:  # A/B: load an alternative build (dervet_hip.build.build_variant)
     _lib.LIB_PATH = sys.argv[2]
 ONLY = sys.argv[3].split(",") if len(sys.argv) > 3 else None
 gs = scenarios.config4(range(S)); pb = builder.pack_groups(gs)
