@@ -84,6 +84,7 @@ struct dvh_handle {
   int last_variant = -1;
   int n_ell = 0, n_generic = 0, n_large = 0, n_band = 0, n_chain = 0;
   int kernel_path = 0;  // 0 band -> ELL -> generic, 1 generic only, 2 ELL -> generic (no band kernel), 3 / 4 as 0
+                        // with the battery form forced, 5 as 0 plus the band kernel's interconnection form
                         // with the battery band kernel's one-step / three-step form forced (0 picks by batch size)
   int cus = 0;          // compute units of the device (band kernel form choice)
   std::vector<int32_t> order;  // dvh_set_launch_order: the next solve's band-pass window order (empty: packing order)
@@ -471,7 +472,7 @@ int dvh_set_launch_order(dvh_handle* h, const int32_t* order, int32_t count) {
 }
 
 int dvh_set_kernel_path(dvh_handle* h, int mode) {
-  if (!h || mode < 0 || mode > 4) return DVH_ERR_ARG;
+  if (!h || mode < 0 || mode > 5) return DVH_ERR_ARG;
   h->kernel_path = mode;
   for (dvh_handle* p : h->peers) p->kernel_path = mode;
   return DVH_OK;
@@ -847,7 +848,8 @@ static int chain_pass(dvh_handle* h, const dvh::Batch& b, const dvh::Work& w, co
 // they take themselves: no setup_kernel for them) -> what that refuses, set up (setup_kernel over the list), through
 // the ELL kernels, in two size classes (the small market-day kernels' shapes, n <= 512 and m <= 768, and the
 // rest), each instantiation sized for its class -> what they refuse (-1) or cannot hold through the generic CSR
-// kernel, both classes in one launch.
+// kernel, both classes in one launch.  With dvh_set_kernel_path 5 the band kernel's interconnection form (POI limit
+// rows, curtailable PV, charge-from-PV rows) runs over the ICE pass's list right behind it.
 // One small read-back per stage that ran ({count, ELL widths, max n / m / nnz} of the windows it hands on; two after
 // the ICE form when it refuses windows: their count, then their size classes once they are set up); a batch the band
 // kernel takes whole waits once.
@@ -901,6 +903,11 @@ static int device_cascade(dvh_handle* h, const dvh::Batch& b, const dvh::Work& w
   if (nsmall - cur > 0) variant = bvar;
   if (cur > 0) {  // pass 2: the band kernel's ICE form over pass 1's refusals
     DVH_HIP(h, dvh::launch_pdhg_band(b, w, ch, o, s, true, form_for(cur), box_ice, L[0], cur, &bvar));
+    // dvh_set_kernel_path 5: the interconnection form (dvh_band_grid.hip) over the same list, behind the ICE form on
+    // the stream: its workgroups leave at once unless their window is still refused (-2), so the route below sees the
+    // final statuses and the mode adds no read-back.  (Which of the two forms took the pass's windows is not read
+    // back either: the pass reports the interconnection form's variant code.)
+    if (h->kernel_path == 5) DVH_HIP(h, dvh::launch_pdhg_band_grid(b, w, ch, o, s, L[0], cur, &bvar));
     DVH_HIP(h, route(1, L[0], cur, -2, 0, 4));
     if (box_ice) DVH_HIP(h, route(2, L[0], cur, -3, 0, 1));
     DVH_HIP(h, readback(1, box_ice ? 2 : 1));

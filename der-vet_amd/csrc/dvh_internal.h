@@ -216,4 +216,11 @@ void comm_destroy(Comm* c);
 hipError_t large_solve(LargeSolver* ls, const Batch& b, int k, const int64_t* d, const Opts& o, const double* hinv,
                        hipStream_t s, std::string* err, float* setup_ms, float* pdhg_ms);
 
+// The band kernel's interconnection form (dvh_band_grid.hip; dvh_set_kernel_path 5): battery windows with POI limit
+// rows, a curtailable-PV column block and / or charge-from-PV rows, one workgroup per listed window.  A workgroup
+// returns at once unless its window's status is -2 (kNeedsEll), so the launch follows the ICE pass over the same
+// list; windows it refuses keep status -2.  variant_out: 9000000 + 200 + waves per window.
+hipError_t launch_pdhg_band_grid(const Batch& b, const Work& w, const Chunk& ch, const Opts& o, hipStream_t s,
+                                 const int32_t* list, int nlist, int* variant_out);
+
 }  // namespace dvh

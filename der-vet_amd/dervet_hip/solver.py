@@ -161,13 +161,15 @@ class BatchSolver:
         self._check(self._lib.dvh_last_host_syncs(self._h, ctypes.byref(v)), "dvh_last_host_syncs")
         return int(v.value)
 
-    _PATHS = {"default": 0, "generic": 1, "ell": 2, "band1": 3, "band3": 4}
+    _PATHS = {"default": 0, "generic": 1, "ell": 2, "band1": 3, "band3": 4, "interconnect": 5}
 
     def set_kernel_path(self, path):
-        """Kernel cascade: "default" (battery-banded -> ELL -> generic CSR), "ell" (ELL -> generic), "generic", or
+        """Kernel cascade: "default" (battery-banded -> ELL -> generic CSR), "ell" (ELL -> generic), "generic",
         "band1" / "band3" (the default cascade with the battery band kernel's form forced: one step per lane, 768
         threads / three steps per lane, 256 threads, two windows per CU; the default picks one-step for batches of
-        at most one battery window per CU).  A bool selects "generic" (True) / "default" (False)."""
+        at most one battery window per CU), or "interconnect" (the default cascade plus the band kernel's
+        interconnection form: windows with POI limit rows, a curtailable-PV block or charge-from-PV rows count as
+        band windows instead of ending on the generic kernel).  A bool selects "generic" (True) / "default" (False)."""
         mode = (1 if path else 0) if isinstance(path, bool) else self._PATHS[path]
         self._check(self._lib.dvh_set_kernel_path(self._h, mode), "dvh_set_kernel_path")
 

@@ -358,7 +358,11 @@ int dvh_last_outage_ms(const dvh_handle* h, double* ms);
  * CSR kernel for every window, 2 = ELL -> generic (no battery-banded kernel), 3 / 4 = as 0 with the battery-banded
  * kernel's form forced: one step per lane (768 threads per window, one window per CU) / three steps per lane (256
  * threads, two windows per CU).  The default picks the one-step form when the batch has at most one battery window
- * per compute unit, else the three-step form. */
+ * per compute unit, else the three-step form.  5 = as 0 plus the band kernel's interconnection form (opt-in): battery
+ * windows with POI import / export limit rows, a curtailable-PV column block (x = [ch, dis, ene, tau, pv]) and / or
+ * charge-from-PV rows (PV grid_charge = 0), which the default cascade hands down to the generic CSR kernel, are
+ * taken after the ICE pass by a 768-thread kernel of their own and counted as band windows; every other window lands
+ * where mode 0 puts it, and the mode adds no host wait. */
 int dvh_set_kernel_path(dvh_handle* h, int mode);
 
 /* Launch order of the next solve (scheduling only: the results do not depend on it).  order: host array, a

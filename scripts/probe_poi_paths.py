@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """POI / PV-curtailment windows (tests/test_gpu_poi.py's rows: MicrogridPOI.py:215-258 import/export limits, charge
 from PV with curtailable PV) at several window lengths, S scenarios each (load scaled per scenario): wall of the
-default route vs the generic CSR kernel (best of 5 after a warm-up), variant and optimal count.
+default route vs the generic CSR kernel vs the band kernel's interconnection form (best of 5 after a warm-up),
+variant and optimal count.
 
 Usage: python scripts/probe_poi_paths.py [S] [lengths, e.g. 240,480,month]
 """
@@ -46,7 +47,7 @@ def main(argv):
             dev = pb.to_torch("cuda:0").alloc_outputs()
             d = np.asarray(pb.desc)
             out = {"kind": kind, "length": n, "windows": pb.count, "n": int(d[:, 0].max()), "m": int(d[:, 1].max())}
-            for path in ("default", "generic"):
+            for path in ("default", "generic", "interconnect"):
                 s.set_kernel_path(path)
                 s.solve_packed(dev)
                 ts = []
