@@ -72,6 +72,14 @@ struct dvh_handle {
   DevBuf s_pairs, s_wts, s_bad;                   // seeded-sweep warm transfer (dvh_sweep.hip)
   DevBuf g_seeds, g_word;                         // scenario series generator (dvh_series.hip)
   DevBuf d_route;                                 // cascade lists' counts / ELL widths (dvh_route.hip)
+  // certificate pass (dvh_certify.hip): its workspace (allocated on first use), the device counters and their pinned
+  // host mirror (copied behind the pass, read at the solve's final wait), the last solve's counts and the pass's events
+  DevBuf c_tptr, c_tind, c_tval, c_tau, c_gx, c_sig, c_gy, c_counts;
+  int32_t* cert_host = nullptr;
+  bool cert_pending = false;
+  int32_t cert[5] = {0, 0, 0, 0, 0};
+  hipEvent_t cert_ev[2] = {nullptr, nullptr};
+  double cert_ms = 0.0;
   int32_t* route_host = nullptr;                  // their pinned host mirror (one small read-back per tier)
   int n_syncs = 0;                                // host waits on the stream in the last solve
   double outage_ms = 0.0;
@@ -150,6 +158,7 @@ static std::string check_options(const dvh_options* o) {
   if (o->check_every <= 0) return "check_every must be > 0";
   if (o->kkt_every <= 0) return "kkt_every must be > 0";
   if (o->kkt_predict < 0) return "kkt_predict must be >= 0";
+  if (o->certify < 0 || o->certify_iters < 0) return "certify and certify_iters must be >= 0";
   if (o->ruiz_iters < 0 || o->power_iters <= 0) return "ruiz_iters must be >= 0 and power_iters > 0";
   if (!(o->step_safety > 0.0 && o->step_safety < 1.0)) return "step_safety must be in (0, 1)";
   if (!(o->reflection >= 0.0 && o->reflection <= 1.0)) return "reflection must be in [0, 1]";
@@ -245,9 +254,13 @@ int dvh_destroy(dvh_handle* h) {
                     &h->w_qs, &h->w_vbuf, &h->w_wbuf, &h->w_tmpc, &h->w_tmpr, &h->w_longk, &h->w_longt, &h->w_scal,
                     &h->w_fc, &h->w_fr,
                     &h->m_list, &h->m_plan, &h->m_pos, &h->m_xbuf, &h->m_abort, &h->o_data, &h->o_cases, &h->o_len, &h->o_hist, &h->o_soe,
-                    &h->s_pairs, &h->s_wts, &h->s_bad, &h->g_seeds, &h->g_word, &h->d_route, &h->d_order, &h->w_queue};
+                    &h->s_pairs, &h->s_wts, &h->s_bad, &h->g_seeds, &h->g_word, &h->d_route, &h->d_order, &h->w_queue,
+                    &h->c_tptr, &h->c_tind, &h->c_tval, &h->c_tau, &h->c_gx, &h->c_sig, &h->c_gy, &h->c_counts};
   for (DevBuf* b : bufs) b->release();
   if (h->route_host) hipHostFree(h->route_host);
+  if (h->cert_host) hipHostFree(h->cert_host);
+  for (auto& e : h->cert_ev)
+    if (e) hipEventDestroy(e);
   for (auto& e : h->ev)
     if (e) hipEventDestroy(e);
   for (auto& ce : h->chunk_events)
@@ -412,6 +425,18 @@ int dvh_synchronize(dvh_handle* h) {
 int dvh_last_host_syncs(const dvh_handle* h, int32_t* out) {
   if (!h || !out) return DVH_ERR_ARG;
   *out = h->n_syncs;
+  return DVH_OK;
+}
+
+int dvh_last_certify(const dvh_handle* h, int32_t* out5) {
+  if (!h || !out5) return DVH_ERR_ARG;
+  for (int i = 0; i < 5; ++i) out5[i] = h->cert[i];
+  return DVH_OK;
+}
+
+int dvh_last_certify_ms(const dvh_handle* h, double* ms) {
+  if (!h || !ms) return DVH_ERR_ARG;
+  *ms = h->cert_ms;
   return DVH_OK;
 }
 
@@ -985,8 +1010,61 @@ static int device_cascade(dvh_handle* h, const dvh::Batch& b, const dvh::Work& w
   return DVH_OK;
 }
 
+// The certificate pass over the batch (dvh_certify.hip), one launch on the solve's stream: after a solve (gate) its
+// workgroups leave at once unless their window came back ITER_LIMIT or NUMERICAL -- the device-side gating of the
+// interconnection form -- so the pass adds no host wait; the counters travel to a pinned host word behind it and are
+// read after the solve's final wait (finish_timing).
+static int certify_pass(dvh_handle* h, const dvh_packed* bt, const std::vector<int64_t>& desc, int gate,
+                        hipStream_t s) {
+  const int count = bt->count;
+  const int64_t bn = desc[6], bm = desc[7], bz = desc[5];
+  int64_t sn = 0, sm = 0, snz = 0;
+  int mn = 1, mm = 1;
+  for (int k = 0; k < count; ++k) {
+    const int64_t* d = &desc[8 * (size_t)k];
+    sn = std::max(sn, d[6] + d[0] - bn);
+    sm = std::max(sm, d[7] + d[1] - bm);
+    snz = std::max(snz, d[5] + d[3] - bz);
+    if (d[0] > dvh::kSmallMax || d[1] > dvh::kSmallMax) continue;
+    mn = std::max<int>(mn, (int)d[0]);
+    mm = std::max<int>(mm, (int)d[1]);
+  }
+  const size_t D = sizeof(double), I = sizeof(int32_t);
+  DVH_HIP(h, h->c_tptr.ensure(I * (size_t)(sn + count)));
+  DVH_HIP(h, h->c_tind.ensure(I * (size_t)snz));
+  DVH_HIP(h, h->c_tval.ensure(D * (size_t)snz));
+  DVH_HIP(h, h->c_tau.ensure(D * (size_t)sn));
+  DVH_HIP(h, h->c_gx.ensure(D * (size_t)sn));
+  DVH_HIP(h, h->c_sig.ensure(D * (size_t)sm));
+  DVH_HIP(h, h->c_gy.ensure(D * (size_t)sm));
+  DVH_HIP(h, h->c_counts.ensure(I * 5));
+  if (!h->cert_host) DVH_HIP(h, hipHostMalloc((void**)&h->cert_host, I * 5, hipHostMallocDefault));
+  for (auto& e : h->cert_ev)
+    if (!e) DVH_HIP(h, hipEventCreate(&e));
+  dvh::Batch b{bt->desc, bt->indptr, bt->indices, bt->data, bt->c, bt->c0, bt->q, bt->l, bt->u,
+               bt->x, bt->y, bt->stats, bt->istats};
+  dvh::CertWork cw{h->c_tptr.as<int32_t>(), h->c_tind.as<int32_t>(), h->c_tval.as<double>(), h->c_tau.as<double>(),
+                   h->c_gx.as<double>(), h->c_sig.as<double>(), h->c_gy.as<double>(), h->c_counts.as<int32_t>(),
+                   bn, bm, bz};
+  const int cap = h->opts.certify_iters > 0 ? h->opts.certify_iters : dvh::kCertifyDefaultCap;
+  DVH_HIP(h, hipMemsetAsync(h->c_counts.p, 0, I * 5, s));
+  DVH_HIP(h, hipEventRecord(h->cert_ev[0], s));
+  DVH_HIP(h, dvh::launch_certify(b, cw, count, mn, mm, cap, gate, s));
+  DVH_HIP(h, hipEventRecord(h->cert_ev[1], s));
+  DVH_HIP(h, hipMemcpyAsync(h->cert_host, h->c_counts.p, I * 5, hipMemcpyDeviceToHost, s));
+  h->cert_pending = true;
+  return DVH_OK;
+}
+
+static void certify_reset(dvh_handle* h) {
+  for (int32_t& v : h->cert) v = 0;
+  h->cert_ms = 0.0;
+  h->cert_pending = false;
+}
+
 static int solve_packed(dvh_handle* h, const dvh_packed* bt, const std::vector<int64_t>& desc, hipStream_t s) {
   const int count = bt->count;
+  certify_reset(h);
   dvh::Opts o;
   o.eps = h->opts.eps;
   o.eps_obj = h->opts.eps_obj;
@@ -1220,6 +1298,23 @@ static int solve_packed(dvh_handle* h, const dvh_packed* bt, const std::vector<i
     if (e != hipSuccess) return fail(h, DVH_ERR_HIP, "window " + std::to_string(k) + ": " + msg);
     ++h->n_large;
   }
+  // the opt-in certificate pass, behind the last tier (off: nothing is launched or allocated)
+  if (h->opts.certify != 0)
+    if (int rc = certify_pass(h, bt, desc, 1, s)) return rc;
+  DVH_HIP(h, hipEventRecord(h->ev[3], s));
+  return DVH_OK;
+}
+
+// dvh_certify_batch on a packed batch: the pass alone, over every window
+static int certify_packed(dvh_handle* h, const dvh_packed* bt, const std::vector<int64_t>& desc, hipStream_t s) {
+  certify_reset(h);
+  h->n_ell = h->n_generic = h->n_large = h->n_band = h->n_chain = 0;
+  h->n_chain_aborts = 0;
+  h->warn.clear();
+  h->large_ms[0] = h->large_ms[1] = 0.0f;
+  h->chunk_used = 0;
+  DVH_HIP(h, hipEventRecord(h->ev[0], s));
+  if (int rc = certify_pass(h, bt, desc, 0, s)) return rc;
   DVH_HIP(h, hipEventRecord(h->ev[3], s));
   return DVH_OK;
 }
@@ -1229,6 +1324,11 @@ static int finish_timing(dvh_handle* h, hipStream_t s) {
   float t = 0;
   h->timing[0] = h->timing[1] = h->timing[2] = 0;
   if (hipEventElapsedTime(&t, h->ev[0], h->ev[3]) == hipSuccess) h->timing[0] = t;
+  if (h->cert_pending) {  // the certificate pass's counters and time (copied behind it on the stream)
+    for (int i = 0; i < 5; ++i) h->cert[i] = h->cert_host[i];
+    if (hipEventElapsedTime(&t, h->cert_ev[0], h->cert_ev[1]) == hipSuccess) h->cert_ms = t;
+    h->cert_pending = false;
+  }
   for (size_t i = 0; i < h->chunk_used; ++i) {
     const auto& ce = h->chunk_events[i];
     if (hipEventElapsedTime(&t, ce[0], ce[1]) == hipSuccess) h->timing[1] += t;
@@ -1239,7 +1339,7 @@ static int finish_timing(dvh_handle* h, hipStream_t s) {
   return DVH_OK;
 }
 
-static int solve_batch_one(dvh_handle* h, const dvh_lp* lps, int32_t count, dvh_result* out);
+static int solve_batch_one(dvh_handle* h, const dvh_lp* lps, int32_t count, dvh_result* out, bool screen = false);
 
 // Contiguous, cost-balanced ranges of the batch for the handle's devices (windows the on-chip kernels take cost one
 // workgroup each; larger windows run grid-wide and cost in proportion to their nonzeros; dervet_hip/parallel.py
@@ -1279,6 +1379,8 @@ extern "C" int dvh_solve_batch(dvh_handle* h, const dvh_lp* lps, int32_t count, 
   if (b[1] > b[0]) rc[0] = solve_batch_one(h, lps, b[1], out);
   for (auto& t : th) t.join();
   int nell = 0, ngen = 0, nlarge = 0, nband = 0, nchain = 0, naborts = 0;
+  int32_t cert[5] = {0, 0, 0, 0, 0};
+  double cert_ms = 0.0;
   std::string warn;
   double setup = 0.0, pdhg = 0.0;
   for (int i = 0; i < P; ++i) {
@@ -1292,6 +1394,9 @@ extern "C" int dvh_solve_batch(dvh_handle* h, const dvh_lp* lps, int32_t count, 
     nlarge += hs[i]->n_large;
     nband += hs[i]->n_band;
     nchain += hs[i]->n_chain;
+    for (int u = 0; u < 4; ++u) cert[u] += hs[i]->cert[u];
+    cert[4] = std::max(cert[4], hs[i]->cert[4]);
+    cert_ms = std::max(cert_ms, hs[i]->cert_ms);
     naborts += hs[i]->n_chain_aborts;
     warn += hs[i]->warn;
     setup = std::max(setup, hs[i]->timing[1]);
@@ -1303,6 +1408,8 @@ extern "C" int dvh_solve_batch(dvh_handle* h, const dvh_lp* lps, int32_t count, 
   h->n_band = nband;
   h->n_chain = nchain;
   h->n_chain_aborts = naborts;
+  for (int u = 0; u < 5; ++u) h->cert[u] = cert[u];
+  h->cert_ms = cert_ms;
   h->warn = warn;
   h->timing[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   h->timing[1] = setup;
@@ -1310,7 +1417,20 @@ extern "C" int dvh_solve_batch(dvh_handle* h, const dvh_lp* lps, int32_t count, 
   return DVH_OK;
 }
 
-static int solve_batch_one(dvh_handle* h, const dvh_lp* lps, int32_t count, dvh_result* out) {
+// The certificate pass alone over host LPs (a screen before a solve): every on-chip window comes back PRIMAL_INFEASIBLE
+// (ray in y), DUAL_INFEASIBLE (ray in x) or DVH_UNDECIDED; x / y of a window are otherwise the caller's.  Runs on the
+// handle's first device.
+extern "C" int dvh_certify_batch(dvh_handle* h, const dvh_lp* lps, int32_t count, dvh_result* out) {
+  if (!h) return DVH_ERR_ARG;
+  if (count < 0 || (count > 0 && (!lps || !out))) return fail(h, DVH_ERR_ARG, "null lps/out or negative count");
+  if (count == 0) {
+    certify_reset(h);
+    return DVH_OK;
+  }
+  return solve_batch_one(h, lps, count, out, true);
+}
+
+static int solve_batch_one(dvh_handle* h, const dvh_lp* lps, int32_t count, dvh_result* out, bool screen) {
   DVH_HIP(h, hipSetDevice(h->device));
   std::vector<int64_t> desc(8 * (size_t)count);
   int64_t tn = 0, tm = 0, tz = 0, tr = 0;
@@ -1377,7 +1497,7 @@ static int solve_batch_one(dvh_handle* h, const dvh_lp* lps, int32_t count, dvh_
   if (tm) DVH_HIP(h, hipMemcpyAsync(h->d_q.p, q.data(), D * tm, hipMemcpyHostToDevice, s));
   DVH_HIP(h, hipMemcpyAsync(h->d_c0.p, c0.data(), D * count, hipMemcpyHostToDevice, s));
   std::vector<double> x0, y0;
-  if (h->opts.warm_start) {  // starting points: the caller's x / y buffers (zero where absent)
+  if (h->opts.warm_start || screen) {  // starting points (the screen: what an undecided window keeps): the caller's x / y buffers (zero where absent)
     x0.assign(tn, 0.0);
     y0.assign(std::max<int64_t>(tm, 1), 0.0);
     for (int k = 0; k < count; ++k) {
@@ -1408,7 +1528,7 @@ static int solve_batch_one(dvh_handle* h, const dvh_lp* lps, int32_t count, dvh_
   bt.stats = h->d_stats.as<double>();
   bt.istats = h->d_istats.as<int32_t>();
   h->n_syncs = 0;
-  int rc = solve_packed(h, &bt, desc, s);
+  int rc = screen ? certify_packed(h, &bt, desc, s) : solve_packed(h, &bt, desc, s);
   if (rc != DVH_OK) return rc;
   std::vector<double> x(tn), y(tm), stats(4 * (size_t)count);
   std::vector<int32_t> ist(2 * (size_t)count);

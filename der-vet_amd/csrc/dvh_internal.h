@@ -223,4 +223,29 @@ hipError_t large_solve(LargeSolver* ls, const Batch& b, int k, const int64_t* d,
 hipError_t launch_pdhg_band_grid(const Batch& b, const Work& w, const Chunk& ch, const Opts& o, hipStream_t s,
                                  const int32_t* list, int nlist, int* variant_out);
 
+// Certificate pass (dvh_certify.hip; dvh_options.certify, dvh_certify_batch): plain PDHG on the unscaled LP of every
+// on-chip window of the batch, one workgroup each, until a Farkas certificate (status 1, the ray in y) or an unbounded
+// ray (status 2, the ray in x) passes its test or `cap` iterations are done.  gate != 0 (after a solve): a workgroup
+// leaves at once unless its window's status is ITER_LIMIT or NUMERICAL, and a window that is not certified is left
+// exactly as it was; gate == 0 (the screen): every window, the undecided ones come back with status 5 (DVH_UNDECIDED).
+// The workspace is the pass's own, indexed by the descriptors' offsets less window 0's (base_*): K' (tptr one extra
+// entry per window), the steps, the last-step candidates.  counts[5] (device, zeroed by the caller) = {windows
+// examined, primal infeasible, dual infeasible, skipped for size (n or m > kSmallMax), largest certificate-iteration
+// count}.  max_n, max_m: the largest on-chip window (the launch's LDS).
+constexpr int kCertifyDefaultCap = 65536;
+struct CertWork {
+  int32_t* tptr;   // [sum n + count]
+  int32_t* tind;   // [sum nnz]
+  double* tval;    // [sum nnz]
+  double* tau;     // [sum n]
+  double* gx;      // [sum n]
+  double* sig;     // [sum m]
+  double* gy;      // [sum m]
+  int32_t* counts; // [5]
+  int64_t base_n, base_m, base_nz;
+};
+size_t certify_lds_bytes(int max_n, int max_m);
+hipError_t launch_certify(const Batch& b, const CertWork& cw, int count, int max_n, int max_m, int cap, int gate,
+                          hipStream_t s);
+
 }  // namespace dvh

@@ -11,9 +11,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DVH_LIB") or os.path.join(HERE, "libdervet_hip.so")
 
 DVH_OK, DVH_ERR_ARG, DVH_ERR_HIP, DVH_ERR_UNSUPPORTED = 0, -1, -2, -3
-OPTIMAL, PRIMAL_INFEASIBLE, DUAL_INFEASIBLE, ITER_LIMIT, NUMERICAL = 0, 1, 2, 3, 4
+OPTIMAL, PRIMAL_INFEASIBLE, DUAL_INFEASIBLE, ITER_LIMIT, NUMERICAL, UNDECIDED = 0, 1, 2, 3, 4, 5
 STATUS_NAMES = {OPTIMAL: "optimal", PRIMAL_INFEASIBLE: "infeasible", DUAL_INFEASIBLE: "unbounded",
-                ITER_LIMIT: "optimal_inaccurate", NUMERICAL: "solver_error"}
+                ITER_LIMIT: "optimal_inaccurate", NUMERICAL: "solver_error",
+                UNDECIDED: "undecided"}  # (BatchSolver.certify only: the certificate pass found neither certificate)
 
 c_int32_p = ctypes.POINTER(ctypes.c_int32)
 c_double_p = ctypes.POINTER(ctypes.c_double)
@@ -26,9 +27,9 @@ class Options(ctypes.Structure):
                 ("reflection", ctypes.c_double), ("restart_sufficient", ctypes.c_double),
                 ("restart_necessary", ctypes.c_double), ("restart_artificial", ctypes.c_double),
                 ("primal_weight_theta", ctypes.c_double), ("verbose", ctypes.c_int32),
-                ("kkt_every", ctypes.c_int32), ("warm_start", ctypes.c_int32), ("pad0", ctypes.c_int32),
+                ("kkt_every", ctypes.c_int32), ("warm_start", ctypes.c_int32), ("certify_iters", ctypes.c_int32),
                 ("eps_obj", ctypes.c_double), ("kkt_predict", ctypes.c_int32),
-                ("reserved", ctypes.c_int32)]
+                ("certify", ctypes.c_int32)]
 
 
 class LP(ctypes.Structure):
@@ -102,6 +103,9 @@ SYMBOLS = {
     "dvh_last_error": (ctypes.c_char_p, [ctypes.c_void_p]),
     "dvh_set_options": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Options)]),
     "dvh_solve_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(LP), ctypes.c_int32, ctypes.POINTER(Result)]),
+    "dvh_certify_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(LP), ctypes.c_int32, ctypes.POINTER(Result)]),
+    "dvh_last_certify": (ctypes.c_int, [ctypes.c_void_p, c_int32_p]),
+    "dvh_last_certify_ms": (ctypes.c_int, [ctypes.c_void_p, c_double_p]),
     "dvh_solve_packed_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Packed), ctypes.c_void_p]),
     "dvh_warm_transfer": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Packed), ctypes.c_void_p, ctypes.c_int32]),
     "dvh_warm_transfer_blend": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Packed), ctypes.c_void_p,
@@ -148,8 +152,10 @@ def load(path=None):
                            "(there is no CPU fallback)")
     lib = ctypes.CDLL(p)
     for name, (res, args) in SYMBOLS.items():
-        if os.environ.get("DVH_LIB") and not hasattr(lib, name):
-            continue  # an A/B build of an earlier library (scripts/): the entry points it has
+        if (path is not None or os.environ.get("DVH_LIB")) and not hasattr(lib, name):
+            # another implementation of the ABI (the CPU restatement, which has no certificate pass), or an A/B build
+            # of an earlier library (scripts/): the entry points it has.  The product library must have them all.
+            continue
         f = getattr(lib, name)
         f.restype = res
         f.argtypes = args

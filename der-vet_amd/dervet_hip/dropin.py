@@ -34,7 +34,12 @@ Failure detection: a window the GPU leaves without a certi
 numerical failure, or an infeasibility / unboundedness verdict -- is re-solved by the reference
 ``solve_optimization`` in place (``retry_failed``, default on), so that DER-VET receives exactly what its own solve
 of that window gives; ``LoopReport`` counts GPU, reference (MILP / non-LP) and retried windows.  With
-``retry_failed=False`` the GPU verdict is saved as ECOS would report it (iteration limit -> optimal_inaccurate).  Scenarios whose windows are coupled through
+``retry_failed=False`` the GPU verdict is saved as ECOS would report it (iteration limit -> optimal_inaccurate).
+GPU certificates (``certify=True``, ``install(certify=True)``; off by default): the solver handle runs with the
+``certify`` option (include/dervet_hip.h: the certificate pass behind every solve), and a window it returns as
+PRIMAL_INFEASIBLE / DUAL_INFEASIBLE -- a Farkas certificate or an unbounded ray that passed its test on the GPU -- is
+saved as ECOS would report it ("infeasible" / "unbounded") without the reference re-solve; ``LoopReport.certified``
+counts them (they count as ``gpu`` windows too).  Scenarios whose windows are coupled through
 saved results (battery degradation, Battery.py:87-110; sizing, MicrogridScenario.py:361-363) cannot batch their
 own windows; ``batched_cases_loop`` batches them ACROSS scenarios instead: window k of every case in one GPU
 call, saved before any case sets up window k + 1 (the serial case loop of dervet/DERVET.py:75-83, in lockstep).
@@ -103,21 +108,23 @@ class CvxpyWindow:
 
 
 RETRY_STATUSES = (_lib.ITER_LIMIT, _lib.NUMERICAL, _lib.PRIMAL_INFEASIBLE, _lib.DUAL_INFEASIBLE)
+CERTIFIED_STATUSES = (_lib.PRIMAL_INFEASIBLE, _lib.DUAL_INFEASIBLE)  # (with certify: the GPU's verdict stands)
 
 
 class LoopReport:
     """Where a loop's windows were solved: ``gpu`` (saved from the batched solve, ``relaxed`` of them MILP
     relaxations), ``reference`` (MILP / non-LP windows solved by ``solve_optimization`` in place) and ``retried``
     (GPU windows without a certified optimum, re-solved by ``solve_optimization``; ``retried_status`` counts them
-    by the cvxpy status string of the GPU verdict)."""
+    by the cvxpy status string of the GPU verdict); ``certified`` of the ``gpu`` windows were saved as infeasible /
+    unbounded on the GPU's certificate (``certify=True`` only)."""
 
     def __init__(self):
-        self.gpu = self.relaxed = self.reference = self.retried = 0
+        self.gpu = self.relaxed = self.reference = self.retried = self.certified = 0
         self.retried_status = {}
 
     def as_dict(self):
         return dict(gpu=self.gpu, relaxed=self.relaxed, reference=self.reference, retried=self.retried,
-                    retried_status=dict(self.retried_status))
+                    retried_status=dict(self.retried_status), certified=self.certified)
 
     def __repr__(self):
         return f"LoopReport({self.as_dict()})"
@@ -185,13 +192,17 @@ def _restore_window_state(scenario, plan):
             der.variables_dict = vd
 
 
-def _solve_plans(plans, solver):
-    """One batched solve over the LP windows of `plans` (list of plan tuples); returns {index: WindowResult}."""
+def _solve_plans(plans, solver, certify=False):
+    """One batched solve over the LP windows of `plans` (list of plan tuples); returns {index: WindowResult}.
+    certify: the handle runs with the certificate pass behind the solve."""
     lp_idx = [i for i, p in enumerate(plans) if p.win is not None]
     if not lp_idx:
         return {}
     own = solver is None
-    solver = solver or BatchSolver(0)
+    if own:
+        solver = BatchSolver(0, certify=1) if certify else BatchSolver(0)
+    elif certify:
+        solver.set_options(certify=1)
     try:
         res = solver.solve([plans[i].win.lp for i in lp_idx])
     finally:
@@ -200,12 +211,17 @@ def _solve_plans(plans, solver):
     return dict(zip(lp_idx, res))
 
 
-def _save(scenario, plan, r, report, retry_failed=True):
+def _save(scenario, plan, r, report, retry_failed=True, certify=False):
     opt_period, sub_index, functions, constraints, _, win, _ = plan
     _restore_window_state(scenario, plan)  # before the in-place reference solves too
     if win is None:  # MILP / non-LP window: the reference solve, in place
         prob, obj, err = scenario.solve_optimization(functions, constraints)
         report.reference += 1
+    elif certify and r.status in CERTIFIED_STATUSES:  # certified on the GPU: saved as ECOS would report it
+        prob, err = win.unpack(r)
+        obj = functions
+        report.gpu += 1
+        report.certified += 1
     elif retry_failed and r.status in RETRY_STATUSES:  # no certified optimum: the reference solve, in place
         prob, obj, err = scenario.solve_optimization(functions, constraints)
         report.retried += 1
@@ -219,7 +235,7 @@ def _save(scenario, plan, r, report, retry_failed=True):
 
 
 def batched_optimize_problem_loop(scenario, solver=None, exporter=None, relax_milp=False, retry_failed=True,
-                                  **kwargs):
+                                  certify=False, **kwargs):
     """Batched ``MicrogridScenario.optimize_problem_loop`` (dervet/MicrogridScenario.py:281-320).  Returns the plan
     list; the window accounting is left on ``scenario.dervet_hip_report`` (a LoopReport)."""
     report = LoopReport()
@@ -241,13 +257,13 @@ def batched_optimize_problem_loop(scenario, solver=None, exporter=None, relax_mi
     exporter = exporter or CvxpyExporter(relax_milp)
     plan = [p for p in (_setup_export(scenario, w, alpha, ignore, exporter)
                         for w in scenario.optimization_levels.predictive.unique()) if p is not None]
-    results = _solve_plans(plan, solver)
+    results = _solve_plans(plan, solver, certify)
     for i, p in enumerate(plan):
-        _save(scenario, p, results.get(i), report, retry_failed)
+        _save(scenario, p, results.get(i), report, retry_failed, certify)
     return plan
 
 
-def batched_cases_loop(scenarios, solver=None, exporter=None, relax_milp=False, retry_failed=True):
+def batched_cases_loop(scenarios, solver=None, exporter=None, relax_milp=False, retry_failed=True, certify=False):
     """The optimize_problem_loop of several cases (dervet/DERVET.py:75-83) batched on the GPU.
 
     Independent cases (``windows_are_independent``) put all their windows into one batch.  Coupled cases
@@ -256,7 +272,8 @@ def batched_cases_loop(scenarios, solver=None, exporter=None, relax_milp=False, 
     Returns the plans per case, in case order; each case's accounting is on its ``dervet_hip_report``."""
     exporter = exporter or CvxpyExporter(relax_milp)
     own = solver is None
-    solver = solver or BatchSolver(0)
+    if own:
+        solver = BatchSolver(0, certify=1) if certify else BatchSolver(0)
     try:
         live, indep, coupled = [], [], []
         for s in scenarios:
@@ -277,9 +294,9 @@ def batched_cases_loop(scenarios, solver=None, exporter=None, relax_milp=False, 
                 p = _setup_export(s, w, alpha, ignore, exporter)
                 if p is not None:
                     flat.append((i, p))
-        res = _solve_plans([p for _, p in flat], solver)
+        res = _solve_plans([p for _, p in flat], solver, certify)
         for k, (i, p) in enumerate(flat):
-            _save(scenarios[i], p, res.get(k), scenarios[i].dervet_hip_report, retry_failed)
+            _save(scenarios[i], p, res.get(k), scenarios[i].dervet_hip_report, retry_failed, certify)
             plans[i].append(p)
         # coupled cases: window position by window position across the cases
         periods = {i: list(scenarios[i].optimization_levels.predictive.unique()) for i in coupled}
@@ -291,9 +308,9 @@ def batched_cases_loop(scenarios, solver=None, exporter=None, relax_milp=False, 
                     p = _setup_export(scenarios[i], periods[i][pos], alpha, ignore, exporter)
                     if p is not None:
                         step.append((i, p))
-            res = _solve_plans([p for _, p in step], solver)
+            res = _solve_plans([p for _, p in step], solver, certify)
             for k, (i, p) in enumerate(step):
-                _save(scenarios[i], p, res.get(k), scenarios[i].dervet_hip_report, retry_failed)
+                _save(scenarios[i], p, res.get(k), scenarios[i].dervet_hip_report, retry_failed, certify)
                 plans[i].append(p)
         return [plans[i] for i in range(len(scenarios))]
     finally:
@@ -301,7 +318,8 @@ def batched_cases_loop(scenarios, solver=None, exporter=None, relax_milp=False, 
             solver.close()
 
 
-def make_batched_scenario_class(base, solver_factory=None, relax_milp=False, retry_failed=True, exporter_factory=None):
+def make_batched_scenario_class(base, solver_factory=None, relax_milp=False, retry_failed=True, exporter_factory=None,
+                                certify=False):
     """Subclass of the reference ``MicrogridScenario`` whose window loop is batched on the GPU."""
 
     class BatchedMicrogridScenario(base):
@@ -310,18 +328,19 @@ def make_batched_scenario_class(base, solver_factory=None, relax_milp=False, ret
             exporter = exporter_factory() if exporter_factory else None
             try:
                 return batched_optimize_problem_loop(self, solver=solver, exporter=exporter, relax_milp=relax_milp,
-                                                     retry_failed=retry_failed, **kwargs)
+                                                     retry_failed=retry_failed, certify=certify, **kwargs)
             finally:
                 if solver is not None:
                     solver.close()
 
     BatchedMicrogridScenario.__name__ = "BatchedMicrogridScenario"
     BatchedMicrogridScenario.dervet_hip_options = (solver_factory, bool(relax_milp), bool(retry_failed))
+    BatchedMicrogridScenario.dervet_hip_certify = bool(certify)  # (with dervet_hip_options: what install compares)
     return BatchedMicrogridScenario
 
 
 def make_batched_dervet_solve(dervet_module, solver_factory=None, relax_milp=False, retry_failed=True,
-                              case_batch=None, exporter_factory=None):
+                              case_batch=None, exporter_factory=None, certify=False):
     """``DERVET.solve`` (dervet/DERVET.py:72-90) with every case's windows in one batched solve.
 
     The reference runs its cases one after the other -- preamble, ``optimize_problem_loop``, ``add_instance`` --
@@ -354,7 +373,7 @@ def make_batched_dervet_solve(dervet_module, solver_factory=None, relax_milp=Fal
             exporter = exporter_factory() if exporter_factory else None
             try:
                 batched_cases_loop(runs, solver=solver, exporter=exporter, relax_milp=relax_milp,
-                                   retry_failed=retry_failed)
+                                   retry_failed=retry_failed, certify=certify)
             finally:
                 if solver is not None:
                     solver.close()
@@ -371,10 +390,12 @@ def make_batched_dervet_solve(dervet_module, solver_factory=None, relax_milp=Fal
 
 
 def install(dervet_module=None, relax_milp=False, retry_failed=True, solver_factory=None, batch_cases=False,
-            case_batch=None, exporter_factory=None):
+            case_batch=None, exporter_factory=None, certify=False):
     """Patch dervet.DERVET.MicrogridScenario (hard-coded at dervet/DERVET.py:76) with the batched class.
     ``relax_milp``: the user's opt-in to GPU LP relaxations of binary = 1 windows (north_star); off, MILP windows stay
     on the reference solve.  ``retry_failed``: re-solve windows without a certified GPU optimum by the reference.
+    ``certify``: the solver factory's handle runs with the GPU certificate pass (``certify`` = 1) and a window it
+    certifies is saved as "infeasible" / "unbounded" without the reference re-solve (``LoopReport.certified``).
     ``batch_cases``: also patch ``DERVET.solve`` (DERVET.py:72-90) so that every case's windows go to the GPU
     together (``make_batched_dervet_solve``; ``case_batch`` cases at a time); off, the reference's serial case loop
     is kept (and a previous ``batch_cases`` install is undone)."""
@@ -382,7 +403,8 @@ def install(dervet_module=None, relax_milp=False, retry_failed=True, solver_fact
         import dervet.DERVET as dervet_module  # noqa: N813
     base = dervet_module.MicrogridScenario
     if getattr(base, "__name__", "") == "BatchedMicrogridScenario":
-        if base.dervet_hip_options == (solver_factory, bool(relax_milp), bool(retry_failed)):
+        if base.dervet_hip_options == (solver_factory, bool(relax_milp), bool(retry_failed)) and \
+                getattr(base, "dervet_hip_certify", False) == bool(certify):
             cls = base
         else:
             base = base.__bases__[0]  # re-install with the new options over the reference class
@@ -390,7 +412,7 @@ def install(dervet_module=None, relax_milp=False, retry_failed=True, solver_fact
     else:
         cls = None
     if cls is None:
-        cls = make_batched_scenario_class(base, solver_factory, relax_milp, retry_failed, exporter_factory)
+        cls = make_batched_scenario_class(base, solver_factory, relax_milp, retry_failed, exporter_factory, certify)
         dervet_module.MicrogridScenario = cls
     driver = getattr(dervet_module, "DERVET", None)
     if driver is not None:
@@ -398,7 +420,7 @@ def install(dervet_module=None, relax_milp=False, retry_failed=True, solver_fact
             driver._dervet_hip_reference_solve = driver.solve
         if batch_cases:
             driver.solve = make_batched_dervet_solve(dervet_module, solver_factory, relax_milp, retry_failed,
-                                                     case_batch, exporter_factory)
+                                                     case_batch, exporter_factory, certify)
         else:
             driver.solve = driver._dervet_hip_reference_solve
     return cls

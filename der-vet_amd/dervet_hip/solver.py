@@ -184,7 +184,30 @@ class BatchSolver:
         """Solve a list of WindowLP on the GPU; returns a list of WindowResult (same order).
 
         start: optional list of (x, y) starting points (unscaled; None entries start cold), used when the
-        solver's ``warm_start`` option is set (battery-banded windows)."""
+        solver's ``warm_start`` option is set (battery-banded windows).
+
+        With the ``certify=1`` option, a window the cascade leaves ITER_LIMIT / NUMERICAL and the certificate pass
+        proves infeasible or unbounded returns status "infeasible" / "unbounded", obj +inf / -inf, the normalised
+        Farkas ray in y / the unbounded ray in x, primal_res_rel = the certificate's margin, dual_res_rel = its
+        violation (include/dervet_hip.h); ``certify_stats()`` counts them."""
+        return self._batch_call("dvh_solve_batch", lps, start)
+
+    def certify(self, lps):
+        """The certificate pass alone (dvh_certify_batch), a screen to run before a solve: a list of WindowResult with
+        status 1 "infeasible" (Farkas ray in y), 2 "unbounded" (ray in x) or 5 "undecided" (x, y zero; windows above
+        the on-chip size too); iters = the pass's iterations.  No window comes back "optimal"."""
+        return self._batch_call("dvh_certify_batch", lps, None)
+
+    def certify_stats(self):
+        """The certificate pass of the last solve / certify call (dvh_last_certify); all 0 when it did not run."""
+        v = (ctypes.c_int32 * 5)()
+        self._check(self._lib.dvh_last_certify(self._h, v), "dvh_last_certify")
+        ms = ctypes.c_double()
+        self._check(self._lib.dvh_last_certify_ms(self._h, ctypes.byref(ms)), "dvh_last_certify_ms")
+        return {"examined": v[0], "primal_infeasible": v[1], "dual_infeasible": v[2], "skipped": v[3],
+                "max_iters": v[4], "ms": float(ms.value)}
+
+    def _batch_call(self, entry, lps, start):
         count = len(lps)
         if count == 0:
             return []
@@ -221,7 +244,7 @@ class BatchSolver:
             outs.append((x, y))
             res[k].x = x.ctypes.data_as(_lib.c_double_p)
             res[k].y = y.ctypes.data_as(_lib.c_double_p) if m else None
-        self._check(self._lib.dvh_solve_batch(self._h, arr, count, res), "dvh_solve_batch")
+        self._check(getattr(self._lib, entry)(self._h, arr, count, res), entry)
         return [WindowResult(outs[k][0], outs[k][1], res[k].obj, res[k].status, res[k].iters, res[k].primal_res_rel,
                              res[k].dual_res_rel, res[k].gap_rel) for k in range(count)]
 

@@ -50,6 +50,7 @@ extern "C" {
 #define DVH_DUAL_INFEASIBLE 2
 #define DVH_ITER_LIMIT 3
 #define DVH_NUMERICAL 4
+#define DVH_UNDECIDED 5 /* dvh_certify_batch only: neither certificate found within the cap */
 
 /* structure hints (dvh_lp.structure) */
 #define DVH_STRUCT_GENERIC_CSR 0
@@ -71,7 +72,7 @@ typedef struct dvh_options {
   int32_t kkt_every;          /* termination (KKT) check every kkt_every restart checks, default 4 */
   int32_t warm_start;         /* 1: start each window from the x / y already in the output buffers     */
                               /*    (unscaled, e.g. a similar window's solution); 0: x = proj(0), y = 0 */
-  int32_t pad0;
+  int32_t certify_iters;      /* iteration cap of the certificate pass (certify below); 0 = default, 65536          */
   double eps_obj;             /* objective-error termination (0 = off), default 1e-6: besides the KKT test, */
                               /* |pobj - dobj| + ||y||_2 ||r_p||_2 <= eps_obj (1 + |pobj|) (unscaled), an    */
                               /* estimate of |pobj - opt| (gap + the dual-weighted primal residual)          */
@@ -80,7 +81,11 @@ typedef struct dvh_options {
                               /* ratio max(pres, dres, gap) / eps scaled by the fixed-point residual's decrease  */
                               /* since then, exceeds P; at most 4 due checks in a row are skipped.  Termination  */
                               /* still needs a KKT check that passes: this only saves hopeless checks.           */
-  int32_t reserved;
+  int32_t certify;            /* 0 = off (default: nothing new is launched or allocated).  1: after the last tier  */
+                              /* of a solve, the certificate pass (dvh_certify_batch below) runs over the batch's  */
+                              /* on-chip windows that came back ITER_LIMIT or NUMERICAL, in one launch gated on    */
+                              /* the device (no extra host wait): a window it certifies returns PRIMAL_INFEASIBLE  */
+                              /* or DUAL_INFEASIBLE with its ray, every other window is left exactly as it was     */
 } dvh_options;
 
 typedef struct dvh_lp {
@@ -283,6 +288,35 @@ int dvh_warm_transfer(dvh_handle* h, const dvh_packed* batch, const int32_t* pai
  * for bit.  DVH_ERR_ARG as dvh_warm_transfer, and for q out of range or a weight that is not finite. */
 int dvh_warm_transfer_blend(dvh_handle* h, const dvh_packed* batch, const int32_t* rows, const double* weights,
                             int32_t count, int32_t q);
+
+/* ---- Infeasibility / unboundedness certificates (no reference counterpart: ECOS / GLPK report "infeasible" or
+ * "unbounded" themselves, cvxpy statuses read at MicrogridScenario.py:348-363; the restarted PDHG kernels can only
+ * prove a window optimal, or infeasible when a column's bounds are crossed).  The pass runs plain PDHG on the
+ * unscaled LP of every on-chip window (n, m <= 4096; one workgroup each), cold (x = proj(0), y = 0), with the
+ * diagonal steps tau_j = 1 / sum_i |K_ij|, sigma_i = 1 / sum_j |K_ij|, and every 64 iterations tests y_k and
+ * y_k - y_{k-1} as Farkas certificates and x_k - x_0 and x_k - x_{k-1} as unbounded rays (on an infeasible LP all
+ * converge to the infimal displacement vector), until one passes or certify_iters iterations are done.
+ *   Farkas (PRIMAL_INFEASIBLE): y with its >= rows clamped at 0 and ||y||_inf = 1, r = K'y,
+ *     viol = max r_j^+ over u_j = +inf, r_j^- over l_j = -inf, margin = q'y - sum_j (r_j > 0 ? u_j r_j : l_j r_j) over
+ *     the finite bounds; certified when margin > 0, viol <= 1e-8 margin, margin >= 1e-9 (sum |q_i y_i| + sum |bound r_j|).
+ *   Ray (DUAL_INFEASIBLE): d with d_j >= 0 where l_j is finite, <= 0 where u_j is finite, ||d||_inf = 1,
+ *     viol = max(||K_E d||_inf, ||(K_I d)^-||_inf); certified when -c'd > 0, viol <= 1e-8 (-c'd), -c'd >= 1e-9 sum |c_j d_j|.
+ * A certified window: status 1 / 2, obj = +INFINITY / -INFINITY, primal_res_rel = margin (-c'd), dual_res_rel = viol,
+ * gap_rel = 0 (stats = {+-INF, margin, viol, 0}), the normalised ray in y (status 1) or x (status 2), the other vector
+ * untouched.  Bit-reproducible run to run (no floating-point atomics, fixed-order reductions).
+ * dvh_certify_batch runs the pass alone over every listed window -- a screen to call before a solve: status 1 / 2 as
+ * above with iters = the pass's iterations, else DVH_UNDECIDED (x, y untouched; windows above the on-chip size too).
+ * A window whose bounds are crossed is PRIMAL_INFEASIBLE at 0 iterations with margin = the largest l_j - u_j and no
+ * ray.  With dvh_options.certify = 1 the same pass follows every solve (dvh_solve_batch and dvh_solve_packed_device,
+ * every kernel path, every device of the handle) over the windows left ITER_LIMIT / NUMERICAL; there iters stays the
+ * main solve's.  Host buffers in / out; blocks; runs on the handle's first device. */
+int dvh_certify_batch(dvh_handle* h, const dvh_lp* lps, int32_t count, dvh_result* out);
+/* The certificate pass of the most recent solve / dvh_certify_batch: out5 = {windows examined (on-chip windows the pass
+ * iterated on), certified primal infeasible, certified dual infeasible, skipped for size (n or m > 4096), largest
+ * iteration count at which a certificate passed}.  All 0 when the pass did not run; reset by every solve. */
+int dvh_last_certify(const dvh_handle* h, int32_t* out5);
+/* Its kernel time (HIP events, milliseconds; 0 when it did not run). */
+int dvh_last_certify_ms(const dvh_handle* h, double* ms);
 
 /* Timing of the most recent solve on the handle's stream (HIP events, milliseconds):
  * [0] whole solve, [1] setup kernel (transpose + scaling + power iteration), [2] PDHG kernels.  On the default
