@@ -105,7 +105,12 @@ struct dvh_handle {
   // thread per device, no inter-device traffic), results written straight into the caller's buffers.
   std::vector<dvh_handle*> peers;
   dvh::Comm* comm = nullptr;  // dvh_comm_init: the result all-gather's RCCL communicator (dvh_comm.cpp)
+  dvh::SizingState* sizing = nullptr;  // reliability sizing (dvh_sizing.cpp): device buffers, last call's timing
 };
+
+namespace dvh {
+HandleView handle_view(dvh_handle* h) { return HandleView{h->device, h->stream, &h->opts, &h->err, &h->sizing}; }
+}  // namespace dvh
 
 // Every host wait on a solve's stream goes through here (dvh_last_host_syncs reports the count of the last solve).
 static hipError_t sync_stream(dvh_handle* h, hipStream_t s) {
@@ -269,6 +274,7 @@ int dvh_destroy(dvh_handle* h) {
   h->chunk_events.clear();
   if (h->large) dvh::large_destroy(h->large);
   if (h->comm) dvh::comm_destroy(h->comm);
+  if (h->sizing) dvh::sizing_destroy(h->sizing);
   if (h->stream) hipStreamDestroy(h->stream);
   delete h;
   return DVH_OK;

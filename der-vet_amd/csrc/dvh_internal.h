@@ -6,6 +6,8 @@
 #include <string>
 
 struct dvh_window_series;  // include/dervet_hip.h
+struct dvh_options;
+struct dvh_handle;
 
 namespace dvh {
 
@@ -197,6 +199,40 @@ hipError_t launch_outage(const OutageCase* d_cases, int ncase, int max_steps_n, 
 // min_soe_iterative mode: soe_used (max - min SOE of a target-length outage from soe0) per start.
 hipError_t launch_outage_min_soe(const OutageCase* d_cases, int ncase, int max_steps_n, double* d_soe_used,
                                  hipStream_t s);
+
+// The sizing loop's scan: d_first[case] (preset to INT32_MAX) <- the smallest uncovered start, d_count[case] (preset
+// to 0) += the number of uncovered starts, of an outage_len-step outage from soe0 at every start.
+hipError_t launch_outage_first_uncovered(const OutageCase* d_cases, int ncase, int max_steps_n, int32_t* d_first,
+                                         int32_t* d_count, hipStream_t s);
+
+// Reliability sizing LP on the device (dvh_sizing.hip; include/dervet_hip.h dvh_sizing_windows): one LP of the packed
+// batch per entry, window `b` of the batch = entry b.  Device pointers; starts[K] are steps of the series.
+struct SizingLP {
+  const double *cl, *pv_vari, *shed;  // [n_steps] critical load, [n_steps] PV x nu or null, [>= L] % kept or null
+  int32_t* starts;                    // [>= K] outage starts; new_start >= 0 is stored at starts[K - 1] first
+  int n_steps, K, L, new_start;
+  double dt, dg_gen, rte, llsoc, ulsoc, a0;  // a0 = min(soc_init, ulsoc)
+  double lE, uE, lP, uP, cE, cP, c0;
+};
+// Expands nlp LPs into the packed arrays through their descriptors (desc[8 b ..], shapes n = 2 + 3 K L, m = 6 K L,
+// m_eq = K L, nnz = 14 K L, checked by the caller).
+hipError_t launch_build_sizing(const SizingLP* d_lps, int nlp, const int64_t* desc, int32_t* indptr, int32_t* indices,
+                               double* data, double* c, double* c0, double* q, double* l, double* u, hipStream_t s);
+// sizes[4 b .. 4 b + 3] = {x[off_n], x[off_n + 1], status, iterations} of window b (the E and P columns).
+hipError_t launch_gather_sizes(const int64_t* desc, const double* x, const int32_t* istats, int nlp, double* sizes,
+                               hipStream_t s);
+
+// What dvh_sizing.cpp needs of a handle (defined next to dvh_handle, dvh_api.cpp).
+struct SizingState;
+struct HandleView {
+  int device;
+  hipStream_t stream;
+  dvh_options* opts;
+  std::string* err;
+  SizingState** sizing;  // owned by the handle, freed by sizing_destroy at dvh_destroy
+};
+HandleView handle_view(dvh_handle* h);
+void sizing_destroy(SizingState* s);
 
 // Grid-wide PDHG for one window too large for the workgroup-per-window kernels (dvh_large.hip).
 struct LargeSolver;

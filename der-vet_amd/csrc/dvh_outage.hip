@@ -34,24 +34,33 @@ __device__ __forceinline__ double pymin3(double a, double b, double c) {
   return r;
 }
 
-// MINSOE = false: covered length per start + histogram (load_coverage_probability :876-967).
-// MINSOE = true: soe_used per start = max - min of the SOE profile including the start (min_soe_iterative
+// MODE kCoverage: covered length per start + histogram (load_coverage_probability :876-967).
+// MODE kMinSoe: soe_used per start = max - min of the SOE profile including the start (min_soe_iterative
 // :685-756, the reliability minimum-SOE requirement), written to soe_used[len_off + t].
-template <bool MINSOE>
+// MODE kFirstUncovered: the sizing loop's scan (find_first_uncovered :391-445): a start is uncovered when the
+// outage_len-step outage from soe0 covers fewer than outage_len steps and fewer than the steps left (:431-435);
+// lengths[case] <- min over the uncovered starts (the caller presets it above every start), hist[case] += their
+// number.  Reduced in the wave by ballot (lanes hold consecutive starts: the lowest set bit is the wave's first),
+// across the workgroup's waves in LDS, then one integer atomicMin and one atomicAdd per workgroup.
+enum { kCoverage = 0, kMinSoe = 1, kFirstUncovered = 2 };
+template <int MODE>
 __global__ __launch_bounds__(kOutB) void outage_kernel(const OutageCase* cases, int32_t* lengths, int32_t* hist,
                                                       double* soe_used) {
 #pragma clang fp contract(off)
+  constexpr bool MINSOE = MODE == kMinSoe, SCAN = MODE == kFirstUncovered;
   extern __shared__ int32_t lh[];  // [outage_len + 1] histogram of this workgroup
+  __shared__ int32_t wfirst[kOutB / kWave], wcount[kOutB / kWave];
   const OutageCase c = cases[blockIdx.y];
   const int nb = c.outage_len + 1;
-  if (!MINSOE) {
+  bool uncovered = false;
+  if (MODE == kCoverage) {
     for (int i = threadIdx.x; i < nb; i += kOutB) lh[i] = 0;
     __syncthreads();
   }
   const int t = blockIdx.x * kOutB + threadIdx.x;
   if (t < c.n_steps) {
     const int stop = min(t + c.max_steps, c.n_steps);  // data_process slices max_steps entries (:462-465)
-    double soe = (!MINSOE && c.init_soe) ? c.init_soe[t] : c.soe0;
+    double soe = (MODE == kCoverage && c.init_soe) ? c.init_soe[t] : c.soe0;
     double smax = soe, smin = soe;
     int k = 0;
     for (; k < c.outage_len; ++k) {
@@ -84,15 +93,37 @@ __global__ __launch_bounds__(kOutB) void outage_kernel(const OutageCase* cases, 
     }
     if (MINSOE) {
       soe_used[c.len_off + t] = smax - smin;
+    } else if (SCAN) {
+      uncovered = k < c.outage_len && k < c.n_steps - t;
     } else {
       if (lengths) lengths[c.len_off + t] = k;
       atomicAdd(&lh[k], 1);
     }
   }
-  if (!MINSOE) {
+  if (MODE == kCoverage) {
     __syncthreads();
     for (int i = threadIdx.x; i < nb; i += kOutB)
       if (lh[i]) atomicAdd(&hist[c.hist_off + i], lh[i]);
+  }
+  if (SCAN) {
+    const unsigned long long mask = __ballot(uncovered);
+    const int wave = threadIdx.x / kWave;
+    if (threadIdx.x % kWave == 0) {
+      wcount[wave] = __popcll(mask);
+      wfirst[wave] = mask ? blockIdx.x * kOutB + wave * kWave + (__ffsll(mask) - 1) : INT32_MAX;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      int n = 0, f = INT32_MAX;
+      for (int w = 0; w < kOutB / kWave; ++w) {
+        n += wcount[w];
+        f = min(f, wfirst[w]);
+      }
+      if (n) {
+        atomicMin(&lengths[blockIdx.y], f);
+        atomicAdd(&hist[blockIdx.y], n);
+      }
+    }
   }
 }
 
@@ -104,7 +135,7 @@ hipError_t launch_outage(const OutageCase* d_cases, int ncase, int max_steps_n, 
   const size_t lds = sizeof(int32_t) * (size_t)max_bins;
   if (lds > 64 * 1024) return hipErrorInvalidValue;
   dim3 grid((max_steps_n + kOutB - 1) / kOutB, ncase);
-  hipLaunchKernelGGL(outage_kernel<false>, grid, dim3(kOutB), lds, s, d_cases, d_lengths, d_hist, nullptr);
+  hipLaunchKernelGGL(outage_kernel<kCoverage>, grid, dim3(kOutB), lds, s, d_cases, d_lengths, d_hist, nullptr);
   return hipGetLastError();
 }
 
@@ -112,7 +143,15 @@ hipError_t launch_outage_min_soe(const OutageCase* d_cases, int ncase, int max_s
                                  hipStream_t s) {
   if (ncase <= 0 || max_steps_n <= 0) return hipSuccess;
   dim3 grid((max_steps_n + kOutB - 1) / kOutB, ncase);
-  hipLaunchKernelGGL(outage_kernel<true>, grid, dim3(kOutB), 0, s, d_cases, nullptr, nullptr, d_soe_used);
+  hipLaunchKernelGGL(outage_kernel<kMinSoe>, grid, dim3(kOutB), 0, s, d_cases, nullptr, nullptr, d_soe_used);
+  return hipGetLastError();
+}
+
+hipError_t launch_outage_first_uncovered(const OutageCase* d_cases, int ncase, int max_steps_n, int32_t* d_first,
+                                         int32_t* d_count, hipStream_t s) {
+  if (ncase <= 0 || max_steps_n <= 0) return hipSuccess;
+  dim3 grid((max_steps_n + kOutB - 1) / kOutB, ncase);
+  hipLaunchKernelGGL(outage_kernel<kFirstUncovered>, grid, dim3(kOutB), 0, s, d_cases, d_first, d_count, nullptr);
   return hipGetLastError();
 }
 

@@ -63,6 +63,27 @@ class OutageCase(ctypes.Structure):
                 ("rte", ctypes.c_double)]
 
 
+class SizingSpec(ctypes.Structure):
+    """dvh_sizing_spec (reliability sizing: what is sized for one outage case)."""
+    _fields_ = [("target_hours", ctypes.c_double), ("size_energy", ctypes.c_int32), ("size_power", ctypes.c_int32),
+                ("ccost", ctypes.c_double), ("ccost_kw", ctypes.c_double), ("ccost_kwh", ctypes.c_double),
+                ("energy_min", ctypes.c_double), ("energy_max", ctypes.c_double), ("power_min", ctypes.c_double),
+                ("power_max", ctypes.c_double), ("energy", ctypes.c_double), ("power", ctypes.c_double),
+                ("llsoc", ctypes.c_double), ("ulsoc", ctypes.c_double), ("soc_init", ctypes.c_double),
+                ("n_seed", ctypes.c_int32), ("max_rounds", ctypes.c_int32)]
+
+
+class SizingResult(ctypes.Structure):
+    """dvh_sizing_result."""
+    _fields_ = [("energy", ctypes.c_double), ("power", ctypes.c_double), ("capex", ctypes.c_double),
+                ("status", ctypes.c_int32), ("lp_status", ctypes.c_int32), ("rounds", ctypes.c_int32),
+                ("n_starts", ctypes.c_int32), ("lp_iters", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("starts", c_int32_p)]
+
+
+SIZING_STATUS_NAMES = {0: "SIZED", 1: "ROUND_LIMIT", 2: "STALLED", 3: "LP_FAILED"}
+
+
 # symbol -> (restype, argtypes); every symbol declared in include/dervet_hip.h
 class BatteryGroup(ctypes.Structure):
     """dvh_battery_group (device-side window builder inputs; pointers are device addresses)."""
@@ -130,6 +151,13 @@ SYMBOLS = {
     "dvh_outage_min_soe": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(OutageCase), ctypes.c_int32, c_int32_p,
                                           c_double_p]),
     "dvh_last_outage_ms": (ctypes.c_int, [ctypes.c_void_p, c_double_p]),
+    "dvh_outage_first_uncovered": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(OutageCase), ctypes.c_int32,
+                                                  c_int32_p, c_int32_p, c_int32_p]),
+    "dvh_sizing_windows": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(OutageCase), ctypes.POINTER(SizingSpec),
+                                          ctypes.c_int32, c_int32_p, c_int32_p, ctypes.POINTER(Result)]),
+    "dvh_size_reliability": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(OutageCase), ctypes.POINTER(SizingSpec),
+                                            ctypes.c_int32, ctypes.POINTER(SizingResult)]),
+    "dvh_last_sizing_ms": (ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p]),
     "dvh_comm_unique_id": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p]),
     "dvh_comm_init": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_char_p]),
     "dvh_comm_info": (ctypes.c_int, [ctypes.c_void_p, c_int32_p]),

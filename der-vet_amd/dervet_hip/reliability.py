@@ -8,6 +8,11 @@ DataFrame (index 'Outage Length (hrs)', column 'Load Coverage Probability (%)').
 follows the reference's choice (:896-905): the 'Aggregated State of Energy (kWh)' results column, the
 'Aggregate Energy Min (kWh)' column for User-constraint-only runs, or soc_init x energy rating
 (``init_soe=None``).  Bit-exact with the numpy reference (tests/test_gpu_outage.py); no CPU fallback.
+
+``size_for_reliability`` is the sizing step of the same value stream (``Reliability.sizing_module`` :153-219): the
+cutting-plane loop that sizes the ESS for an outage target, for a batch of cases in one library call
+(``dvh_size_reliability``; the sizing LP of lp/sizing.py built on the device, the scan of every start as one launch of
+the outage kernel).  ``first_uncovered`` and ``sizing_windows`` expose its two halves.
 """
 import ctypes
 from dataclasses import dataclass, field
@@ -32,6 +37,24 @@ class OutageCase:
     n_2: bool = False                         # N-2: drop the largest generator (dg_rating)
     dg_rating: float = 0.0
     load_shed_pct: np.ndarray = None          # [max_outage_duration] % of critical load kept per outage hour
+
+
+@dataclass
+class SizingSpec:
+    """What ``size_for_reliability`` sizes for one OutageCase (Reliability.sizing_module's inputs).  The case's
+    ``ess`` dict supplies rte, llsoc, ulsoc and the rating that is not sized; 0 = no user limit."""
+    target_hours: float                       # Reliability 'target': outage length to ride through
+    size_energy: bool = True
+    size_power: bool = True
+    ccost: float = 0.0                        # $ (constant)
+    ccost_kw: float = 0.0                     # $/kW, > 0 when power is sized
+    ccost_kwh: float = 0.0                    # $/kWh, > 0 when energy is sized
+    user_energy_min: float = 0.0
+    user_energy_max: float = 0.0
+    user_power_min: float = 0.0
+    user_power_max: float = 0.0
+    n_seed: int = 10                          # outage starts of the first round (top_n_outages)
+    max_rounds: int = 256
 
 
 def der_mix_properties(case):
@@ -118,6 +141,129 @@ def min_soe(cases, target_hours, solver):
         res.append(out[a:a + N])
         a += N
     return res
+
+
+def first_uncovered(cases, target_hours, solver):
+    """The sizing loop's scan (Reliability.find_first_uncovered, :391-445) for every case at once: an outage of
+    round(target_hours / dt) steps simulated from every start from soc_init x energy rating (``init_soe`` ignored);
+    a start is uncovered when fewer steps are covered than the target and than the series has left.  Returns
+    (first, n_uncovered): int32 arrays, first = the smallest uncovered start or -1.  Bit-exact with the oracle."""
+    lib = solver._lib
+    arr, keep, _ = _cases_struct(cases)
+    hours = np.broadcast_to(np.asarray(target_hours, np.float64), (len(cases),))
+    steps = np.array([int(round(h / c.dt)) for h, c in zip(hours, cases)], np.int32)
+    first = np.zeros(len(cases), np.int32)
+    count = np.zeros(len(cases), np.int32)
+    solver._check(lib.dvh_outage_first_uncovered(solver._h, arr, len(cases), steps.ctypes.data_as(_lib.c_int32_p),
+                                                 first.ctypes.data_as(_lib.c_int32_p),
+                                                 count.ctypes.data_as(_lib.c_int32_p)), "dvh_outage_first_uncovered")
+    return first, count
+
+
+def _spec_struct(cases, specs):
+    """dvh_sizing_spec per case (validated by lp.sizing.terms: ValueError)."""
+    from .lp import sizing
+    if len(cases) != len(specs):
+        raise ValueError("one SizingSpec per OutageCase")
+    arr = (_lib.SizingSpec * len(cases))()
+    for k, (c, sp) in enumerate(zip(cases, specs)):
+        t = sizing.terms(c, sp)
+        o = arr[k]
+        o.target_hours = float(sp.target_hours)
+        o.size_energy, o.size_power = int(bool(sp.size_energy)), int(bool(sp.size_power))
+        o.ccost, o.ccost_kw, o.ccost_kwh = float(sp.ccost), float(sp.ccost_kw), float(sp.ccost_kwh)
+        o.energy_min, o.energy_max, o.power_min, o.power_max = t["lE"], t["uE"], t["lP"], t["uP"]
+        o.energy, o.power = t["lE"], t["lP"]  # (the fixed rating when the quantity is not sized)
+        o.llsoc, o.ulsoc, o.soc_init = t["llsoc"], t["ulsoc"], t["soc_init"]
+        o.n_seed, o.max_rounds = int(sp.n_seed), int(sp.max_rounds)
+    return arr
+
+
+def sizing_windows(cases, specs, starts, solver):
+    """The sizing LP of every case over the given outage starts (``starts[k]``: steps of case k's series), built on
+    the device from the resident series and solved as one batch with the solver's options (dvh_sizing_windows).
+    Returns a WindowResult per case; bit-identical to ``solver.solve([lp.sizing.sizing_lp(c, s, st) ...])``."""
+    from .lp import sizing
+    from .solver import WindowResult
+    lib = solver._lib
+    arr, keep, _ = _cases_struct(cases)
+    sarr = _spec_struct(cases, specs)
+    if len(starts) != len(cases):
+        raise ValueError("one list of starts per case")
+    ns = np.array([len(s) for s in starts], np.int32)
+    flat = np.ascontiguousarray(np.concatenate([np.asarray(s, np.int32).ravel() for s in starts]), np.int32)
+    res = (_lib.Result * len(cases))()
+    outs = []
+    for k, (c, sp) in enumerate(zip(cases, specs)):
+        KL = int(ns[k]) * sizing.outage_steps(c, sp)
+        x, y = np.zeros(2 + 3 * KL), np.zeros(6 * KL)
+        outs.append((x, y))
+        res[k].x = x.ctypes.data_as(_lib.c_double_p)
+        res[k].y = y.ctypes.data_as(_lib.c_double_p)
+    solver._check(lib.dvh_sizing_windows(solver._h, arr, sarr, len(cases), flat.ctypes.data_as(_lib.c_int32_p),
+                                         ns.ctypes.data_as(_lib.c_int32_p), res), "dvh_sizing_windows")
+    return [WindowResult(outs[k][0], outs[k][1], res[k].obj, res[k].status, res[k].iters, res[k].primal_res_rel,
+                         res[k].dual_res_rel, res[k].gap_rel) for k in range(len(cases))]
+
+
+@dataclass
+class SizingResult:
+    energy: float                             # kWh
+    power: float                              # kW (charge = discharge rating)
+    status: str                               # SIZED, ROUND_LIMIT (the last candidate), STALLED, LP_FAILED
+    rounds: int                               # LPs solved
+    capex: float                              # ccost + ccost_kw power + ccost_kwh energy
+    starts: np.ndarray                        # outage starts of the last LP
+    lp_status: int                            # dvh_result.status of the last LP (LP_FAILED: why)
+    lp_iters: int                             # PDHG iterations summed over the rounds
+    min_soe: np.ndarray = None                # with_min_soe: the sized case's 'Reliability Min State of Energy (kWh)'
+
+
+def sized_case(case, result):
+    """``case`` with the ratings of ``result`` (charge = discharge rating), starting every outage from soc_init."""
+    import dataclasses
+    ess = dict(case.ess, E=result.energy, P_ch=result.power, P_dis=result.power)
+    return dataclasses.replace(case, ess=ess, init_soe=None)
+
+
+def size_for_reliability(cases, specs, solver, with_min_soe=False):
+    """Reliability.sizing_module (:153-219) for every case at once: the integer ESS energy and / or power rating that
+    rides through a ``target_hours`` outage from every start of the series, found by the reference's cutting-plane
+    loop in one library call (dvh_size_reliability) with the series resident on the GPU.  Returns a SizingResult per
+    case; with_min_soe adds the sized case's minimum-SOE series (one ``min_soe`` call, as the reference at :209-214;
+    needs whole target hours)."""
+    lib = solver._lib
+    arr, keep, _ = _cases_struct(cases)
+    sarr = _spec_struct(cases, specs)
+    res = (_lib.SizingResult * len(cases))()
+    bufs = []
+    for k, sp in enumerate(specs):
+        b = np.zeros(int(sp.n_seed) + int(sp.max_rounds), np.int32)
+        bufs.append(b)
+        res[k].starts = b.ctypes.data_as(_lib.c_int32_p)
+    solver._check(lib.dvh_size_reliability(solver._h, arr, sarr, len(cases), res), "dvh_size_reliability")
+    out = [SizingResult(res[k].energy, res[k].power, _lib.SIZING_STATUS_NAMES[res[k].status], res[k].rounds,
+                        res[k].capex, bufs[k][:res[k].n_starts].copy(), res[k].lp_status, res[k].lp_iters)
+           for k in range(len(cases))]
+    if with_min_soe:
+        idx = [k for k, r in enumerate(out) if r.energy > 0]
+        hours = [specs[k].target_hours for k in idx]
+        if any(h != int(h) for h in hours):
+            raise ValueError("with_min_soe needs whole target hours (Reliability.outage_duration is an int)")
+        if idx:
+            ms = min_soe([sized_case(cases[k], out[k]) for k in idx], [int(h) for h in hours], solver)
+            for k, v in zip(idx, ms):
+                out[k].min_soe = v
+    return out
+
+
+def last_sizing_ms(solver):
+    """HIP-event time of the last size_for_reliability call: total, LP builds + solves, scans (ms), and rounds summed
+    over the cases."""
+    ms = ctypes.c_double()
+    o3 = (ctypes.c_double * 3)()
+    solver._check(solver._lib.dvh_last_sizing_ms(solver._h, ctypes.byref(ms), o3), "dvh_last_sizing_ms")
+    return {"total_ms": ms.value, "lp_ms": o3[0], "scan_ms": o3[1], "rounds": int(o3[2])}
 
 
 def load_coverage_probability(cases, solver):

@@ -388,6 +388,78 @@ int dvh_outage_min_soe(dvh_handle* h, const dvh_outage_case* cases, int32_t coun
 /* Kernel time of the last dvh_outage_coverage / dvh_outage_min_soe call (HIP events, milliseconds). */
 int dvh_last_outage_ms(const dvh_handle* h, double* ms);
 
+/* ---- Reliability sizing (Reliability.sizing_module, dervet/MicrogridValueStreams/Reliability.py:153-219): the
+ * cutting-plane loop that sizes the ESS for an outage target -- solve a sizing LP over a set of outage starts
+ * (size_for_outages :221-274), simulate an outage from every start of the series (find_first_uncovered :391-445), add
+ * the first start the candidate size fails, repeat.
+ *
+ * The scan.  For every case, an outage of target_steps[k] steps simulated from every start from soe0 (init_soe
+ * ignored, as in dvh_outage_min_soe; the per-step arithmetic of dvh_outage_coverage, bit-exact); a start t is
+ * uncovered when covered < target_steps[k] and covered < n_steps - t (:431-435).  first[k] = the smallest uncovered
+ * start or -1, n_uncovered[k] = their number (host arrays [count]; integer atomics, exact).  1 <= target_steps[k] <=
+ * max_outage (the simulation's data window). */
+int dvh_outage_first_uncovered(dvh_handle* h, const dvh_outage_case* cases, int32_t count, const int32_t* target_steps,
+                               int32_t* first, int32_t* n_uncovered);
+
+/* What is sized for one case.  The case supplies the series, dt, rte, dg_gen, pv_vari and load_shed_pct; its soe0,
+ * soe_min, soe_max, charge_max, discharge_max, init_soe and gamma's energy check are the simulation's and are
+ * overwritten per candidate (soe0 = soc_init E, soe_min / soe_max = llsoc / ulsoc E, charge_max = discharge_max = P). */
+typedef struct dvh_sizing_spec {
+  double target_hours;            /* L = round-half-even(target_hours / dt) steps, 1 <= L <= max_outage           */
+  int32_t size_energy, size_power; /* at least one; a sized quantity needs a positive unit cost                    */
+  double ccost, ccost_kw, ccost_kwh; /* capex = ccost + ccost_kw P + ccost_kwh E                                   */
+  double energy_min, energy_max;  /* bounds of a sized E (max: +INFINITY for none)                                 */
+  double power_min, power_max;    /* bounds of a sized P                                                           */
+  double energy, power;           /* the rating that is not sized                                                  */
+  double llsoc, ulsoc, soc_init;  /* fractions                                                                     */
+  int32_t n_seed, max_rounds;     /* starts of the first round (>= 1), round limit (1 .. 65536)                    */
+} dvh_sizing_spec;
+
+/* The sizing LP of every case over given outage starts, built on the device from the resident series and solved as
+ * one batch with the handle's options: per case k over its starts S = starts[sum n_starts[<k] ..] (K = n_starts[k]
+ * >= 1 steps of the series) and L steps,
+ *   x = [E, P | per window w: ch[0..L-1], dis[0..L-1], s[0..L-1]]  (n = 2 + 3 K L; s_k = energy after step k)
+ *   KL equalities (window-major): s_k - s_{k-1} - rte dt ch_k + dt dis_k = 0,  s_{-1} = min(soc_init, ulsoc) E
+ *   5 KL >= rows, per (w, k): ulsoc E - s_k >= 0, s_k - llsoc E >= 0, P - ch_k >= 0, P - dis_k >= 0,
+ *     dis_k - ch_k >= d,  d = shed_k cl[i] - dg_gen - pv_vari[i], i = t_w + k, shed_k = load_shed_pct[k] / 100 or 1
+ *     (d = 0 for i >= n_steps)
+ *   min ccost_kwh E + ccost_kw P + ccost;  dispatch columns in [0, inf), a sized E / P in its bounds, else fixed.
+ * Bit-identical to dervet_hip/lp/sizing.py sizing_lp (tests/test_gpu_sizing.py).  out[k]: dvh_result of case k (x [n],
+ * y [6 K L] caller-allocated or NULL).  Blocks. */
+int dvh_sizing_windows(dvh_handle* h, const dvh_outage_case* cases, const dvh_sizing_spec* specs, int32_t count,
+                       const int32_t* starts, const int32_t* n_starts, dvh_result* out);
+
+#define DVH_SIZING_SIZED 0
+#define DVH_SIZING_ROUND_LIMIT 1 /* max_rounds rounds done; energy / power = the last candidate                     */
+#define DVH_SIZING_STALLED 2     /* the scan kept returning a start already in the LP                               */
+#define DVH_SIZING_LP_FAILED 3   /* an LP did not come back optimal: lp_status = its dvh_result.status              */
+typedef struct dvh_sizing_result {
+  double energy, power;           /* kWh, kW (integers unless a lower bound or a fixed rating is not)              */
+  double capex;                   /* ccost + ccost_kw power + ccost_kwh energy                                     */
+  int32_t status;                 /* DVH_SIZING_*                                                                  */
+  int32_t lp_status;              /* status of the case's last LP                                                  */
+  int32_t rounds;                 /* LPs solved for this case                                                      */
+  int32_t n_starts;               /* outage starts in its last LP                                                  */
+  int32_t lp_iters;               /* PDHG iterations summed over its LPs                                           */
+  int32_t reserved;
+  int32_t* starts;                /* caller-allocated [n_seed + max_rounds] or NULL: those starts                  */
+} dvh_sizing_result;
+
+/* The loop, for `count` cases at once.  The series are uploaded once; the outage starts are seeded with the first
+ * n_seed indices of a stable descending sort of requirement_t = dt sum_{j<L} cl[t + j] (summed in step order, cut at
+ * the series end; :120-122,170-174).  Per round, over the unfinished cases: (1) build and solve the LPs in one batched
+ * solve with eps = eps_obj = min(the handle's, 1e-8) (the handle's options are restored); (2) candidate of a sized
+ * quantity = ceil(x - delta), delta = 1e-7 max(1, |x|), floored at its lower bound (the reference's integer size
+ * variables, ESSSizing.py:83,98, relaxed and rounded up); (3) the candidate's limits written into the device case
+ * structs; (4) the scan; (5) first < 0: SIZED; first already among the starts: (3)-(4) once more with ceil(x + delta),
+ * STALLED if it still is; else the start is appended.  Host traffic per round: the case structs and descriptors.
+ * Blocks; runs on the handle's first device. */
+int dvh_size_reliability(dvh_handle* h, const dvh_outage_case* cases, const dvh_sizing_spec* specs, int32_t count,
+                         dvh_sizing_result* out);
+/* Time of the last dvh_size_reliability call (HIP events, milliseconds); out3 (or NULL) = {LP builds + solves,
+ * scans, rounds summed over the cases}. */
+int dvh_last_sizing_ms(const dvh_handle* h, double* ms, double* out3);
+
 /* Kernel cascade (testing / A-B timing): 0 = default (battery-banded -> ELL -> generic CSR), 1 = generic
  * CSR kernel for every window, 2 = ELL -> generic (no battery-banded kernel), 3 / 4 = as 0 with the battery-banded
  * kernel's form forced: one step per lane (768 threads per window, one window per CU) / three steps per lane (256
