@@ -113,6 +113,15 @@ class WindowSeries(ctypes.Structure):
                [(f, ctypes.c_void_p) for f in ("rows", "ar", "site_load", "pv_profile", "price", "load_scale",
                                                "price_scale", "pv_rated", "hp", "c0_add", "base", "retail", "c0")]
 
+class DegradationState(ctypes.Structure):
+    """dvh_degradation_state ([S] device arrays of a degradation.Degradation; pointers are device addresses)."""
+    _fields_ = [("incl_cycle_degrade", ctypes.c_int32), ("reserved", ctypes.c_int32)] + \
+               [(f, ctypes.c_void_p) for f in ("e_rated", "yearly", "soh", "replaceable", "degrade_perc",
+                                               "replacements", "skipped", "capacity", "degradation", "reached")]
+
+
+RAINFLOW_MAX_T, RAINFLOW_MAX_TABLE = 20351, 64  # DVH_RAINFLOW_MAX_T, DVH_RAINFLOW_MAX_TABLE
+
 SYMBOLS = {
     "dvh_version": (ctypes.c_char_p, []),
     "dvh_default_options": (None, [ctypes.POINTER(Options)]),
@@ -158,6 +167,13 @@ SYMBOLS = {
     "dvh_size_reliability": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(OutageCase), ctypes.POINTER(SizingSpec),
                                             ctypes.c_int32, ctypes.POINTER(SizingResult)]),
     "dvh_last_sizing_ms": (ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p]),
+    "dvh_cycle_damage": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                                        ctypes.c_void_p, ctypes.c_void_p]),
+    "dvh_degradation_update": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Packed), ctypes.c_int32, ctypes.c_int32,
+                                              ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_double,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                                              ctypes.POINTER(DegradationState), ctypes.c_void_p]),
     "dvh_comm_unique_id": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p]),
     "dvh_comm_init": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_char_p]),
     "dvh_comm_info": (ctypes.c_int, [ctypes.c_void_p, c_int32_p]),

@@ -460,6 +460,53 @@ int dvh_size_reliability(dvh_handle* h, const dvh_outage_case* cases, const dvh_
  * scans, rounds summed over the cases}. */
 int dvh_last_sizing_ms(const dvh_handle* h, double* ms, double* out3);
 
+/* ---- Battery degradation on the device (Battery.py:69-110 through storagevet's BatteryTech degradation, restated in
+ * dervet_hip/degradation.py; the one feature that couples a scenario's windows).  Rainflow counting (ASTM E1049-85
+ * section 5.4.4 as the `rainflow` package writes it: reversals, three-point stack, leftovers as half cycles) of an SOE
+ * profile, each cycle's depth = range / rated energy looked up in the cycle-life table (the first row whose upper limit
+ * is >= the depth, the last row above them all), damage = sum of count / cycle life in extraction order.  One wave per
+ * profile, the profile in LDS, one lane counting: no floating-point atomics, bit-identical to
+ * degradation.cycle_damage and run to run (tests/test_gpu_rainflow.py).  Both calls are asynchronous on `stream` (a
+ * hipStream_t; NULL = the handle's stream, i.e. after its solves), wait for nothing and allocate nothing.
+ * T above DVH_RAINFLOW_MAX_T (the profile no longer fits a workgroup's LDS) is DVH_ERR_UNSUPPORTED: there is no host
+ * fallback.  n_table: 1 .. DVH_RAINFLOW_MAX_TABLE rows, upper ascending.  All pointers are device pointers.
+ *
+ * dvh_cycle_damage: damage_out[s] = the damage of row s of ene[S][row_stride] (its first T entries, row_stride >= T)
+ * with rated energy e_rated[s]; T < 2 gives 0.  The device form of degradation.cycle_damage. */
+#define DVH_RAINFLOW_MAX_T 20351
+#define DVH_RAINFLOW_MAX_TABLE 64
+int dvh_cycle_damage(dvh_handle* h, const double* ene, int64_t row_stride, int32_t S, int32_t T, const double* e_rated,
+                     const double* upper, const double* life, int32_t n_table, double* damage_out, void* stream);
+
+/* Degradation state of S batteries, [S] device arrays (dervet_hip.degradation.Degradation's, element for element). */
+typedef struct dvh_degradation_state {
+  int32_t incl_cycle_degrade;     /* 0: the module is off, calendar loss included (Battery.py:82, :101)             */
+  int32_t reserved;
+  const double* e_rated;          /* in: rated energy, kWh                                                          */
+  const double* yearly;           /* in: calendar degradation, % per year                                           */
+  const double* soh;              /* in: state of health at which the battery is worn, fraction of rated            */
+  const int32_t* replaceable;     /* in: 1 = reset to nameplate when worn                                           */
+  double* degrade_perc;           /* in/out: accumulated degradation, fraction                                      */
+  int64_t* replacements;          /* in/out                                                                         */
+  int64_t* skipped;               /* in/out: windows whose dispatch was not used                                    */
+  double* capacity;               /* out: max(e_rated (1 - degrade_perc), 0) after the update: the next window's E  */
+  double* degradation;            /* out: this window's degradation                                                 */
+  int32_t* reached;               /* out: 1 = worn in this window (before any replacement)                          */
+} dvh_degradation_state;
+
+/* Degradation.update on the device, for the S windows first .. first + S - 1 of a solved packed batch: battery s is
+ * updated from window first + s, whose SOE profile is x[off_n + ene_col .. + T - 1] (battery windows: ene_col = 2 T)
+ * and whose dispatch counts when istats status is DVH_OPTIMAL.  Per battery, in Degradation.update's operations and
+ * order: d = yearly / 100 * (days / 365); a counted window adds cycle damage * (1 - eol_condition / 100), any other
+ * takes the calendar loss only and skipped += 1; degrade_perc += d; reached = capacity <= e_rated * soh; a replaceable
+ * battery that reached it gets degrade_perc = 0, replacements += 1.  The descriptors live on the device, so a window
+ * whose profile does not lie inside it (ene_col + T > n, or the window outside x) is caught there: it is treated as
+ * not counted, never read.  incl_cycle_degrade = 0: nothing is updated; degradation = 0, reached = 0 and the unchanged
+ * capacity are written.  state->capacity may be handed to dvh_build_battery_group as the next position's E. */
+int dvh_degradation_update(dvh_handle* h, const dvh_packed* batch, int32_t first, int32_t S, int32_t T,
+                           int32_t ene_col, double days, double eol_condition, const double* upper, const double* life,
+                           int32_t n_table, const dvh_degradation_state* state, void* stream);
+
 /* Kernel cascade (testing / A-B timing): 0 = default (battery-banded -> ELL -> generic CSR), 1 = generic
  * CSR kernel for every window, 2 = ELL -> generic (no battery-banded kernel), 3 / 4 = as 0 with the battery-banded
  * kernel's form forced: one step per lane (768 threads per window, one window per CU) / three steps per lane (256
