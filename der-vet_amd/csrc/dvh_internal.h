@@ -1,4 +1,4 @@
-// Internal declarations shared by the C-ABI layer (dvh_api.cpp) and the HIP kernels (dvh_kernels.hip).
+// Internal declarations shared by the C-ABI layer (dvh_api*.cpp, dvh_solve.cpp, dvh_cascade.cpp) and the HIP kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -6,6 +6,8 @@
 #include <string>
 
 struct dvh_window_series;  // include/dervet_hip.h
+struct dvh_battery_group;
+struct dvh_packed;
 struct dvh_options;
 struct dvh_handle;
 
@@ -176,6 +178,8 @@ hipError_t launch_series_draws(const uint64_t* seeds, int count, int steps, int 
                                double* z0, double* ar, double* unif, int32_t* ambiguous, int32_t* amb_rows,
                                hipStream_t s);
 hipError_t launch_series_windows(const ::dvh_window_series& w, int32_t* bad, hipStream_t s);
+// Device builder (dvh_build.hip): windows first .. first + g.G - 1 of the packed batch written from the group's series.
+hipError_t launch_build_battery(const ::dvh_battery_group& g, const ::dvh_packed& b, int first, hipStream_t s);
 // Cascade lists on the device (dvh_route.hip): the small windows of [first, first + count) -- or of in_list[0 ..
 // count) -- whose status is `want` (cls 1: and n <= lim_n, m <= lim_m; cls 2: the others; cls 0: any size), in order,
 // to out_list; out_info[0..5] = {their number, max ELL widths wx, wy, max n, m, nnz} over them.
@@ -222,7 +226,8 @@ hipError_t launch_build_sizing(const SizingLP* d_lps, int nlp, const int64_t* de
 hipError_t launch_gather_sizes(const int64_t* desc, const double* x, const int32_t* istats, int nlp, double* sizes,
                                hipStream_t s);
 
-// What dvh_sizing.cpp needs of a handle (defined next to dvh_handle, dvh_api.cpp).
+// What dvh_sizing.cpp and dvh_degradation.hip need of a handle (the other host units include dvh_handle.h;
+// handle_view is in dvh_api.cpp, and the sizing sanitizer driver has a stand-in).
 struct SizingState;
 struct HandleView {
   int device;

@@ -7,36 +7,17 @@
 // (find_first_uncovered :391-445, 8,760 Python simulations per round) becomes one launch of the outage kernel's
 // first-uncovered mode (dvh_outage.hip).  The series are uploaded once; per round only the case structs, the LP
 // descriptors and a few words per case cross the bus.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
 #include <cmath>
-#include <cstring>
 #include <numeric>
 #include <string>
-#include <vector>
 
-#include "../../include/dervet_hip.h"
-#include "dvh_internal.h"
+#include "dvh_host.h"
 #include "dvh_sizing_validate.h"
 
 namespace dvh {
 
-struct SizingBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  hipError_t ensure(size_t want) {
-    if (want <= bytes) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
-    want = std::max<size_t>(want + want / 4, 256);  // the LPs grow by one window per round
-    hipError_t e = hipMalloc(&p, want);
-    if (e == hipSuccess) bytes = want;
-    return e;
-  }
-  template <class T>
-  T* as() const { return static_cast<T*>(p); }
+struct SizingBuf : DevBuf {
+  SizingBuf() { slack_div = 4; }  // the LPs grow by one window per round
 };
 
 struct SizingState {
@@ -44,19 +25,13 @@ struct SizingState {
       count;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // whole call; the phase being timed
   double ms = 0.0, out3[3] = {0.0, 0.0, 0.0};
+  ~SizingState() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
 };
 
-void sizing_destroy(SizingState* s) {
-  if (!s) return;
-  SizingBuf* bufs[] = {&s->series, &s->cases, &s->lps, &s->starts, &s->desc, &s->indptr, &s->indices, &s->data,
-                       &s->c, &s->c0, &s->q, &s->l, &s->u, &s->x, &s->y, &s->stats, &s->istats, &s->sizes, &s->first,
-                       &s->count};
-  for (SizingBuf* b : bufs)
-    if (b->p) (void)hipFree(b->p);
-  for (hipEvent_t e : s->ev)
-    if (e) (void)hipEventDestroy(e);
-  delete s;
-}
+void sizing_destroy(SizingState* s) { delete s; }
 
 }  // namespace dvh
 
@@ -96,45 +71,11 @@ int state(const HandleView& v, SizingState** out) {
 // steps[k] steps from soe0 (init_soe dropped: the sizing scan starts every outage from soe0).
 int upload_series(const HandleView& v, SizingState* st, const dvh_outage_case* cases, int count,
                   const std::vector<int>& steps, std::vector<dvh::OutageCase>& oc) {
-  size_t nd = 0;
-  for (int k = 0; k < count; ++k) {
-    const dvh_outage_case& c = cases[k];
-    nd += (size_t)c.n_steps * (1 + (c.pv_max ? 1 : 0) + (c.pv_vari ? 1 : 0)) +
-          (c.load_shed_pct ? (size_t)c.max_outage : 0);
-  }
-  std::vector<double> data(std::max<size_t>(nd, 1));
+  std::vector<double> data = dvh::outage_stage(cases, count, false);
   SZ_HIP(v, st->series.ensure(sizeof(double) * data.size()));
-  const double* dbase = st->series.as<double>();
-  size_t off = 0;
-  auto put = [&](const double* src, size_t n) -> const double* {
-    if (!src) return nullptr;
-    std::memcpy(&data[off], src, sizeof(double) * n);
-    const double* d = dbase + off;
-    off += n;
-    return d;
-  };
-  oc.assign(count, dvh::OutageCase{});
-  for (int k = 0; k < count; ++k) {
-    const dvh_outage_case& c = cases[k];
-    dvh::OutageCase& o = oc[k];
-    o.n_steps = c.n_steps;
-    o.max_steps = c.max_outage;
-    o.outage_len = steps[k];
-    o.dt = c.dt;
-    o.soe0 = c.soe0;
-    o.dg_gen = c.dg_gen;
-    o.gamma = c.gamma;
-    o.soe_min = c.soe_min;
-    o.soe_max = c.soe_max;
-    o.charge_max = c.charge_max;
-    o.discharge_max = c.discharge_max;
-    o.rte = c.rte;
-    o.critical_load = put(c.critical_load, c.n_steps);
-    o.pv_max = put(c.pv_max, c.n_steps);
-    o.pv_vari = put(c.pv_vari, c.n_steps);
-    o.init_soe = nullptr;
-    o.load_shed = put(c.load_shed_pct, c.max_outage);
-  }
+  oc.resize(count);
+  dvh::outage_stage_fill(cases, count, false, data, st->series.as<double>(), oc.data());
+  for (int k = 0; k < count; ++k) oc[k].outage_len = steps[k];
   SZ_HIP(v, hipMemcpyAsync(st->series.p, data.data(), sizeof(double) * data.size(), hipMemcpyHostToDevice, v.stream));
   SZ_HIP(v, hipStreamSynchronize(v.stream));  // the staging vector ends here
   return DVH_OK;
@@ -246,25 +187,10 @@ int build_batch(const HandleView& v, SizingState* st, const std::vector<dvh::Siz
                                           st->l.as<double>(), st->u.as<double>(), s);
   if (e != hipSuccess) return fail(v, DVH_ERR_HIP, std::string("launch_build_sizing: ") + hipGetErrorString(e));
   SZ_HIP(v, hipStreamSynchronize(s));  // desc and lps are the caller's vectors
-  bt = dvh_packed{};
-  bt.count = n;
-  bt.total_n = tn;
-  bt.total_m = tm;
-  bt.total_nnz = tz;
-  bt.total_rows = tr;
-  bt.desc = st->desc.as<int64_t>();
-  bt.indptr = st->indptr.as<int32_t>();
-  bt.indices = st->indices.as<int32_t>();
-  bt.data = st->data.as<double>();
-  bt.c = st->c.as<double>();
-  bt.c0 = st->c0.as<double>();
-  bt.q = st->q.as<double>();
-  bt.l = st->l.as<double>();
-  bt.u = st->u.as<double>();
-  bt.x = st->x.as<double>();
-  bt.y = st->y.as<double>();
-  bt.stats = st->stats.as<double>();
-  bt.istats = st->istats.as<int32_t>();
+  bt = dvh_packed{n, 0, tn, tm, tz, tr, st->desc.as<int64_t>(), st->indptr.as<int32_t>(), st->indices.as<int32_t>(),
+                  st->data.as<double>(), st->c.as<double>(), st->c0.as<double>(), st->q.as<double>(),
+                  st->l.as<double>(), st->u.as<double>(), st->x.as<double>(), st->y.as<double>(),
+                  st->stats.as<double>(), st->istats.as<int32_t>()};
   return DVH_OK;
 }
 

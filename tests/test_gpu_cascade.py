@@ -1,4 +1,4 @@
-"""GPU: the kernel cascade with its lists formed on the device (csrc/dvh_route.hip, dvh_api.cpp device_cascade) on a
+"""GPU: the kernel cascade with its lists formed on the device (csrc/dvh_route.hip, dvh_cascade.cpp device_cascade) on a
 batch that mixes every tier the drop-in can send at once (dervet/DERVET.py:75-83 puts every case's windows in one
 batch): Usecase 3 market days, config-4 monthly windows, config-5 LP-relaxed ICE windows, POI + curtailable-PV
 windows, annual hourly windows and the 5-minute annual window.  Each tier takes its windows (the next tier is sized for
