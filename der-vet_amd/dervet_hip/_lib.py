@@ -122,6 +122,28 @@ class DegradationState(ctypes.Structure):
 
 RAINFLOW_MAX_T, RAINFLOW_MAX_TABLE = 20351, 64  # DVH_RAINFLOW_MAX_T, DVH_RAINFLOW_MAX_TABLE
 
+
+class BillGroup(ctypes.Structure):
+    """dvh_bill_group (the bill of a group's solved windows; pointers are device addresses)."""
+    _fields_ = [("T", ctypes.c_int32), ("J", ctypes.c_int32), ("G", ctypes.c_int32), ("mI", ctypes.c_int32),
+                ("dt", ctypes.c_double), ("has_pv", ctypes.c_int32), ("has_ice", ctypes.c_int32)] + \
+               [(f, ctypes.c_void_p) for f in ("dcm_t", "dcm_j", "base", "orig", "retail", "da", "demand", "om",
+                                               "ice_cost")]
+
+
+class ValuationArgs(ctypes.Structure):
+    """dvh_valuation (opt_years and win_ptr_host are host arrays, every other pointer a device address)."""
+    _fields_ = [("S", ctypes.c_int32), ("Y", ctypes.c_int32), ("n_opt", ctypes.c_int32), ("n_extra", ctypes.c_int32),
+                ("n_win", ctypes.c_int64), ("n_bills", ctypes.c_int64), ("opt_years", c_int32_p),
+                ("win_ptr_host", c_int64_p)] + \
+               [(f, ctypes.c_void_p) for f in ("win_ptr", "win_idx", "win_year", "bills", "bad")] + \
+               [("rate", ctypes.c_double), ("growth", ctypes.c_double * 5)] + \
+               [(f, ctypes.c_void_p) for f in ("capex", "fixed_om", "extra")]
+
+
+# DVH_BILL_ROWS, DVH_BILL_MAX_J, DVH_CBA_MAX_YEARS, DVH_CBA_MAX_EXTRA, DVH_CBA_FIXED_COLS, DVH_VALUE_COLS
+BILL_ROWS, BILL_MAX_J, CBA_MAX_YEARS, CBA_MAX_EXTRA, CBA_FIXED_COLS, VALUE_COLS = 8, 16, 64, 16, 7, 7
+
 SYMBOLS = {
     "dvh_version": (ctypes.c_char_p, []),
     "dvh_default_options": (None, [ctypes.POINTER(Options)]),
@@ -174,6 +196,11 @@ SYMBOLS = {
                                               ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_double,
                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
                                               ctypes.POINTER(DegradationState), ctypes.c_void_p]),
+    "dvh_bill_windows": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(BillGroup), ctypes.POINTER(Packed), ctypes.c_int32,
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "dvh_value_scenarios": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ValuationArgs), ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "dvh_last_valuation_ms": (ctypes.c_int, [ctypes.c_void_p, c_double_p]),
     "dvh_comm_unique_id": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p]),
     "dvh_comm_init": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_char_p]),
     "dvh_comm_info": (ctypes.c_int, [ctypes.c_void_p, c_int32_p]),

@@ -38,6 +38,7 @@ class WindowGroup:
     u: np.ndarray           # f64 [G, n]
     terms: dict = field(default_factory=dict)   # key -> (coef [G, n], const [G])
     tags: list = field(default_factory=list)    # per-window identifiers (scenario, window)
+    inputs: dict = None     # battery_group: the compact series the bill reads (valuation.BillInputs fields)
 
     @property
     def G(self):
@@ -244,8 +245,17 @@ def battery_group(T, dt, base_load, bat, retail_price=None, da_price=None, deman
     for coef, const in terms.values():
         c += coef
         c0 += const
+    inputs = dict(T=T, J=J, dt=float(dt), dcm_t=np.concatenate(rows_i).astype(np.int32) if rows_i else np.zeros(0, np.int32),
+                  dcm_j=np.concatenate([np.full(len(r_), j) for j, r_ in enumerate(rows_i)]).astype(np.int32)
+                  if rows_i else np.zeros(0, np.int32), base=base,
+                  retail=None if retail_price is None else _col(retail_price, G, T),
+                  da=None if da_price is None else _col(da_price, G, T),
+                  demand=None if not J else np.asarray(demand_prices, np.float64).reshape(G, J),
+                  om=_col(bat.get("OMexpenses", 0.0), G), has_pv=ipv >= 0,
+                  ice_cost=None if ice is None else (_col(ice["efficiency"], G) * _col(ice["fuel_cost"], G)
+                                                     + _col(ice.get("variable_om_cost", 0.0), G)) * dt)
     return WindowGroup(T=T, J=J, m_eq=T + 1, indptr=indptr.astype(np.int32), indices=indices, data=data, c=c, c0=c0,
-                       q=q, l=l, u=u, terms=terms, tags=list(tags) if tags is not None else [None] * G)
+                       q=q, l=l, u=u, terms=terms, tags=list(tags) if tags is not None else [None] * G, inputs=inputs)
 
 
 def _assemble(G, m, blocks):

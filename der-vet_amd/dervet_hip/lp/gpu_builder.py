@@ -130,7 +130,8 @@ def desc_of(specs):
 
 def pack_specs_device(specs, solver, device="cuda:0"):
     """One device PackedBatch (outputs allocated) holding every spec's windows, built on the GPU by the
-    solver's handle (its stream; synchronised before returning)."""
+    solver's handle (its stream; synchronised before returning).  ``.series``: per spec, the device tensors of the
+    series a bill of these windows reads again (valuation.bill_windows), so that they are uploaded once."""
     import torch
     desc, sz = desc_of(specs)
     dev = torch.device(device)
@@ -156,21 +157,33 @@ def pack_specs_device(specs, solver, device="cuda:0"):
         keep.append(x)
         return x.data_ptr()
 
+    def held(a):  # the device tensor up() just handed to the library
+        return None if a is None else (a if isinstance(a, torch.Tensor) else keep[-1])
+
     first = 0
+    series = []
     for s in specs:
         g = _lib.BatteryGroup()
         g.T, g.J, g.G, g.mI, g.dt = s.T, s.J, s.G, len(s.dcm_t), s.dt
         g.has_retail, g.has_da = int(s.retail is not None), int(s.da is not None)
         g.has_emin, g.has_emax = int(s.emin is not None), int(s.emax is not None)
-        g.dcm_t, g.dcm_j = up(s.dcm_t, torch.int32), up(s.dcm_j, torch.int32)
-        g.base, g.retail, g.da, g.demand = up(s.base), up(s.retail), up(s.da), up(s.demand)
+        ser = {}
+        for name, t in (("dcm_t", torch.int32), ("dcm_j", torch.int32), ("base", torch.float64),
+                        ("retail", torch.float64), ("da", torch.float64), ("demand", torch.float64)):
+            setattr(g, name, up(getattr(s, name), t))
+            ser[name] = held(getattr(s, name))
         g.emin, g.emax = up(s.emin), up(s.emax)
         for k, v in s.scal.items():
             setattr(g, k, up(v))
+            if k == "om":
+                ser["om"] = held(v)
         g.c0 = up(s.c0)
         if s.ice:
             g.has_ice = 1
-            g.ice_cap, g.ice_pmin, g.ice_cost = up(s.ice["cap"]), up(s.ice["pmin"]), up(s.ice["cost"])
+            g.ice_cap, g.ice_pmin = up(s.ice["cap"]), up(s.ice["pmin"])
+            g.ice_cost = up(s.ice["cost"])
+            ser["ice_cost"] = held(s.ice["cost"])
+        series.append(ser)
         torch.cuda.synchronize(dev)
         rc = solver._lib.dvh_build_battery_group(solver._h, ctypes.byref(g), ctypes.byref(p), first)
         if rc != 0:
@@ -178,4 +191,6 @@ def pack_specs_device(specs, solver, device="cuda:0"):
         first += s.G
     solver._check(solver._lib.dvh_synchronize(solver._h), "dvh_synchronize")
     del keep
+    # what a bill of these windows reads again (valuation.bill_windows): the uploaded series stay referenced
+    pb.series = series
     return pb

@@ -507,6 +507,100 @@ int dvh_degradation_update(dvh_handle* h, const dvh_packed* batch, int32_t first
                            int32_t ene_col, double days, double eol_condition, const double* upper, const double* life,
                            int32_t n_table, const dvh_degradation_state* state, void* stream);
 
+/* ---- Scenario valuation on the device (dervet/CBA.py:215-233, 299-346, 479-523 on storagevet's Financial, which is
+ * absent; restated as far as the Usecase 2 goldens simple_monthly_bill / pro_forma / npv / payback / cost_benefit pin
+ * it, dervet_hip/valuation.py): the monthly bill of every solved window, then per scenario the pro forma, its present
+ * values, payback and IRR, so that a sweep learns which scenarios are worth building without its dispatch leaving HBM.
+ * Both calls are asynchronous on `stream` (a hipStream_t; NULL = the handle's stream, i.e. after its solves), wait for
+ * nothing and allocate no device memory (the handle's first call creates its timing events).  No floating-point
+ * atomics, fixed-order reductions: bit-identical run to run, and the bill bit-identical to valuation.bill_windows_host.
+ * Not restated (zero in every golden; a caller passes them through `extra`): taxes and MACRS, replacement, salvage and
+ * decommissioning, ECC.  All pointers are device pointers unless marked host.
+ *
+ * dvh_bill_windows: the bill of windows first .. first + G - 1 of a solved packed batch, one 256-thread workgroup per
+ * window.  x is read through the descriptors in builder.battery_group's layout [ch, dis, ene, tau, pv?, elec?, on?]
+ * (has_pv: a curtailable-PV block of T columns after tau; has_ice: elec and on after that); the series are the compact
+ * arrays of dvh_battery_group (the same device arrays may be passed) plus `orig`, the site load alone.  Per step
+ *   net_t = ((base_t + ch_t) - dis_t) - pv_t - elec_t                       (adds and subtracts only, in this order)
+ * and bills[g][0 .. DVH_BILL_ROWS - 1] =
+ *   [0] retail energy charge  sum_t (retail_t dt) net_t              [5] the same of orig_t (the golden "Original")
+ *   [1] demand charge  sum_j demand_j max_{rows i, dcm_j[i] = j} net_{dcm_t[i]}, in j order   [6] the same of orig
+ *   [2] DA energy cost  sum_t (da_t dt) net_t                        [7] the same of orig
+ *   [3] variable O&M  (om / 1000 dt) sum_t dis_t                     [4] ICE fuel  ice_cost sum_t elec_t
+ * (a missing price series bills 0; a tau column without rows bills 0).  The peaks are the dispatch's own, not tau,
+ * which is only within solver tolerance of them; peaks (or NULL) [G][J] receives them in kW.  A window whose istats
+ * status is not DVH_OPTIMAL, or whose descriptor puts a needed column outside its n or the window outside x, is never
+ * read: rows 0 - 4 and its peaks are NaN, rows 5 - 7 are written, and bad[g] = 1 (else 0; + 2 when a demand-charge row
+ * named no step or no tau column and was skipped).  J above DVH_BILL_MAX_J is DVH_ERR_UNSUPPORTED. */
+#define DVH_BILL_ROWS 8
+#define DVH_BILL_MAX_J 16
+typedef struct dvh_bill_group {
+  int32_t T, J, G, mI;             /* steps, tau columns, windows, demand-charge rows                            */
+  double dt;                       /* hours per step                                                             */
+  int32_t has_pv, has_ice;         /* column blocks after tau                                                    */
+  const int32_t* dcm_t;            /* [mI] step of each demand-charge row                                        */
+  const int32_t* dcm_j;            /* [mI] its tau column                                                        */
+  const double* base;              /* [G*T] net load + housekeeping power, kW (dvh_battery_group base)           */
+  const double* orig;              /* [G*T] site load alone, kW, or NULL: base                                   */
+  const double* retail;            /* [G*T] $/kWh or NULL                                                        */
+  const double* da;                /* [G*T] $/kWh or NULL                                                        */
+  const double* demand;            /* [G*J] $/kW                                                                 */
+  const double* om;                /* [G] variable O&M, $/MWh, or NULL: 0                                        */
+  const double* ice_cost;          /* [G] $/kW per step (dvh_battery_group ice_cost); has_ice                    */
+} dvh_bill_group;
+int dvh_bill_windows(dvh_handle* h, const dvh_bill_group* group, const dvh_packed* batch, int32_t first,
+                     double* bills, double* peaks, int32_t* bad, void* stream);
+
+/* dvh_value_scenarios: one thread per scenario.  Scenario s owns the CSR entries win_ptr[s] .. win_ptr[s + 1] - 1:
+ * win_idx[e] is a row of `bills`, win_year[e] the pro forma year it belongs to (0 = the first year after the CAPEX
+ * row), listed in (opt year, window) order -- a seeded sweep packs its seeds first, so a scenario's windows are
+ * scattered.  The pro forma has Y + 1 rows (row 0 = the CAPEX year) and C = DVH_CBA_FIXED_COLS + n_extra columns:
+ *   [0] -capex[s] in row 0;  [1] avoided energy charge, [2] avoided demand charge, [3] DA value: original - with-DER,
+ *   [4] -variable O&M, [5] -fuel: in an opt year the sum over that year's windows in CSR order; a year that is not an
+ *   opt year takes the nearest earlier opt year's value times (1 + growth / 100)^(years since), years before the first
+ *   opt year are de-escalated from it (one opt year: exactly the golden rows; several: UNPINNED);
+ *   [6] -fixed_om[s] in every year, unescalated;  [7 ..] extra[j][0 .. Y] verbatim, shared by the scenarios (the
+ *   golden's Tax Credit, Other Incentives, User Constraints Value, or anything DER-VET computes elsewhere).
+ * values[s][0 .. DVH_VALUE_COLS - 1] =
+ *   [0] lifetime present value  sum_k net_k / (1 + rate)^k, k = 0 at the CAPEX row (numpy's old np.npv)
+ *   [1] present-value cost, [2] present-value benefit: each column discounted on its own; one with a negative present
+ *       value adds its magnitude to the cost, one with a positive to the benefit (the golden cost_benefit row)
+ *   [3] benefit / cost (CBA.py:510-523), NaN when |cost| <= 1e-8.  The golden payback file's "Cost-Benefit Ratio" is
+ *       the inverse, from an older reference version: [1] and [2] are what is pinned
+ *   [4] payback  capex / net_1 with capex = -net_0;  [5] discounted payback  ln(1 / (1 - capex rate / net_1)) /
+ *       ln(1 + rate), NaN when the argument is <= 0 (rate = 0: the payback); both NaN when net_1 <= 0
+ *   [6] IRR with np.irr's meaning (CBA.py:498-507): the real rate above -1 at which the NPV is 0, nearest to 0:
+ *       bracketed on the grid 1 + rate = (17/16)^i, i = -128 .. 128, outward from rate 0, bisected to 1e-13; NaN when no
+ *       grid interval brackets a sign change
+ * valid[s] = 0 when any of the scenario's windows is flagged in `bad`, names no row of bills or a year that is not an
+ * opt year, when a listed opt year has no window, or when win_ptr (device) is not what win_ptr_host said; else 1.
+ * proforma (or NULL) [S][Y + 1][C] receives the full pro forma. */
+#define DVH_CBA_MAX_YEARS 64
+#define DVH_CBA_MAX_EXTRA 16
+#define DVH_CBA_FIXED_COLS 7
+#define DVH_VALUE_COLS 7
+typedef struct dvh_valuation {
+  int32_t S, Y, n_opt, n_extra;    /* scenarios, years after the CAPEX row, opt years, extra columns             */
+  int64_t n_win, n_bills;          /* len(win_idx), rows of bills                                                */
+  const int32_t* opt_years;        /* host [n_opt] ascending, 0 <= . < Y                                         */
+  const int64_t* win_ptr_host;     /* host [S + 1]: validated before the launch                                  */
+  const int64_t* win_ptr;          /* [S + 1] the same on the device                                             */
+  const int32_t* win_idx;          /* [n_win]                                                                    */
+  const int32_t* win_year;         /* [n_win]                                                                    */
+  const double* bills;             /* [n_bills][DVH_BILL_ROWS] (dvh_bill_windows)                                */
+  const int32_t* bad;              /* [n_bills] its flags, or NULL                                               */
+  double rate;                     /* npv discount rate, fraction, > -1                                          */
+  double growth[5];                /* %/yr of columns 1 .. 5                                                     */
+  const double* capex;             /* [S] $                                                                      */
+  const double* fixed_om;          /* [S] $/yr                                                                   */
+  const double* extra;             /* [n_extra][Y + 1] $                                                         */
+} dvh_valuation;
+int dvh_value_scenarios(dvh_handle* h, const dvh_valuation* v, double* values, int32_t* valid, double* proforma,
+                        void* stream);
+/* Kernel times of the handle's most recent dvh_bill_windows and dvh_value_scenarios (HIP events, milliseconds;
+ * 0 for one that has not run): ms2 = {bill, valuation}.  Waits for those two kernels. */
+int dvh_last_valuation_ms(const dvh_handle* h, double* ms2);
+
 /* Kernel cascade (testing / A-B timing): 0 = default (battery-banded -> ELL -> generic CSR), 1 = generic
  * CSR kernel for every window, 2 = ELL -> generic (no battery-banded kernel), 3 / 4 = as 0 with the battery-banded
  * kernel's form forced: one step per lane (768 threads per window, one window per CU) / three steps per lane (256
