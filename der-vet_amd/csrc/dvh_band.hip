@@ -65,8 +65,9 @@ static_assert(band_lds_bytes(kBandSteps / 3, 3, false, true) == 77328, "three-st
 static_assert(band_lds_bytes(kBandSteps, 1, false, false) == 84192, "one-step battery form");
 static_assert(band_lds_bytes(kBandSteps, 1, true, false) == 145632, "ICE form");
 
-// How the ICE form (168-VGPR budget, already spilling) differs from the battery forms.
-template <bool ICE>
+// How the forms differ: the ICE form (168-VGPR budget, already spilling) from the battery forms, and the three-step
+// battery form (S = 3, the bench's) from the one-step one.
+template <bool ICE, int S>
 struct BandTune {
   // the KKT helpers below inlined into the check (out of line every call binds the caller's live registers to the call
   // ABI; battery +0.8-1.5 %, profiles/r05s_check_cost_*.log; ICE -5.6 % inlined, profiles/r05za_config5_bisect.log)
@@ -78,11 +79,18 @@ struct BandTune {
   // wave 0 anyway (ICE 116.5k -> 126.0k; battery within its spread at +10 spilled VGPRs, profiles/r06l_pin_kx.log)
   static constexpr bool pin_kx = ICE;
   // the check path's wave-uniform doubles through v_readfirstlane, held in SGPR pairs between checks (ICE spills
-  // 41 -> 19, config 5 +1.3 %; battery 1.8 % slower, profiles/r06r_uscal.log)
-  static constexpr bool uniform_check_scalars = ICE;
+  // 41 -> 19, config 5 +1.3 %, profiles/r06r_uscal.log; the three-step battery form with the plain-iteration loop
+  // spills 47 -> 22 VGPRs, bench 371.6 -> 363.9 ms per step, profiles/band_loop_variants.log -- before that loop it
+  // ran 1.8 % slower with them; the one-step battery form keeps its VGPR copies)
+  static constexpr bool uniform_check_scalars = ICE || S == 3;
   // the objective gate's dual-residual term sum_j |r_d,j| |x_j| (kkt_done; the extra reduced value cost the ICE form
   // 6 % on config 5 at unchanged iterations, profiles/r04ab_ab_kkt_rdx.log: its windows keep the round-3 test)
   static constexpr bool gate_rdx = !ICE;
+  // the plain iterations between two checks in an innermost loop of their own, one per wave kind (see the solve loop):
+  // three-step battery form bench 392.6-394.7 -> 371.5-371.7 ms per step, one-step battery form config 1 13.1k -> 15.7k
+  // and config 2 15.0-15.2k -> 16.8-16.9k windows/s; the ICE form spills 66 VGPRs instead of 19 with it and ran
+  // config 5 at 131.0k against 131.2k windows/s (profiles/band_loop_variants.log)
+  static constexpr bool plain_loop = !ICE;
 };
 // Wave 0, whose primal half-step carries the tau column's reduction and update -- the iteration's critical path, on
 // which the other waves wait at the first barrier -- runs that half-step at this s_setprio level, so that the SIMD it
@@ -179,16 +187,16 @@ __device__ __forceinline__ double fma_clamp01(double a, double b, double c) {
   return r;
 }
 
-// a check-path wave-uniform double, made scalar where BandTune says so
-template <bool ICE>
+// a check-path wave-uniform double, made scalar where BandTune says so (USC = BandTune::uniform_check_scalars)
+template <bool USC>
 __device__ __forceinline__ double usc(double v) {
-  return BandTune<ICE>::uniform_check_scalars ? uniform(v) : v;
+  return USC ? uniform(v) : v;
 }
 // a uniform double the optimiser must re-read where it is used (so that what is formed from it is not hoisted out of the
 // iteration loop into a long-lived VGPR pair)
-template <bool ICE>
+template <bool USC>
 __device__ __forceinline__ double sgpr_fresh(double v) {
-  if constexpr (BandTune<ICE>::uniform_check_scalars) asm volatile("" : "+s"(v));
+  if constexpr (USC) asm volatile("" : "+s"(v));
   return v;
 }
 template <int B, int S, bool ICE, bool LC, int WPS, bool GATE, bool BOX>
@@ -199,7 +207,8 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
   // the kernel writes global memory the compiler does not treat the descriptors as constant -- they sat in VGPR pairs,
   // and the base addresses the set-up and the write-back use were spilled
   const int k = __builtin_amdgcn_readfirstlane(k_in);
-  using Tune = BandTune<ICE>;
+  using Tune = BandTune<ICE, S>;
+  constexpr bool USC = Tune::uniform_check_scalars;
   constexpr int NW = B / kWave;
   constexpr int SB = S * B;        // step capacity
   constexpr int NC = ICE ? 5 : 3;  // columns per step: ch, dis, ene (, elec, on)
@@ -1202,8 +1211,35 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
   using F = std::integral_constant<bool, false>;
   using Tt = std::integral_constant<bool, true>;
   pstamp(-1);
+  // The plain iterations between two checks run in an innermost loop of their own, one per wave kind
+  // (Tune::plain_loop).  As `if (--ck != 0) { iterate; continue; }` in this loop, the plain iteration was a branch of
+  // the one region LLVM makes of the loop over windows and this loop: every iteration left it through a chain of about
+  // ten flag-driven scalar branches and a block of 17 v_mov_b64 that copied the new x, y, tau and init-row values back
+  // to the registers the next iteration reads (the phis were not coalesced), at the head of wave 0's primal half-step.
+  // The inner loops keep those values in place (scripts/loop_shape.py, profiles/band_loop_shape.txt).
+  // Same iterations, same checks: ck - 1 plain iterations precede the check at ck = 1, fewer where max_iters comes first
+  // (the loop then ends without a check, as before); it, kin and ck end up as the one-by-one form leaves them.
+  // Barriers: np comes from ck, o.max_iters and it, which are the same in every wave of the workgroup (kernel arguments
+  // and counters every wave advances alike), so every wave runs the same number of trips, the exit is a scalar branch
+  // on an SGPR counter, and both loop bodies pass the iteration's two barriers once per trip on every path (what differs
+  // between the two, and what their lane masks skip, holds no barrier) -- the waves of a workgroup, some in one loop and
+  // some in the other, meet at every barrier.  (The two traps of the persistent loop below apply here as well: a
+  // lane-dependent trip count would be structurized into a loop whose barriers the waves do not reach in step.)
   while (it < o.max_iters) {
-    if (--ck != 0) {
+    if constexpr (Tune::plain_loop) {
+      if (ck > 1) {  // the ck - 1 plain iterations up to the next check, or those left to max_iters
+        int np = min(ck - 1, o.max_iters - it);
+        ck -= np;
+        if (w0) {
+          do iterate(F(), Tt());
+          while (--np != 0);
+        } else {
+          do iterate(F(), F());
+          while (--np != 0);
+        }
+        continue;
+      }
+    } else if (--ck != 0) {
       if (w0)
         iterate(F(), Tt());
       else
@@ -1237,7 +1273,7 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
       block_sum1<B, 4, true>(acc4, red);
 #pragma unroll
       for (int u = 0; u < 4; ++u) acc[u] = acc4[u];
-      r = usc<ICE>(sqrt(pw * acc[0] + acc[2] / pw));
+      r = usc<USC>(sqrt(pw * acc[0] + acc[2] / pw));
       if (kkt && !last && kkt_gate_skip(o, gate, r)) {
         kkt = false;
         ++gate.skip;
@@ -1359,12 +1395,12 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
 #pragma unroll
       for (int u = 0; u < 4; ++u) acc[u] = acc4[u];
     }
-    if constexpr (!GATE) r = usc<ICE>(sqrt(pw * acc[0] + acc[2] / pw));
+    if constexpr (!GATE) r = usc<USC>(sqrt(pw * acc[0] + acc[2] / pw));
     if (kkt) {
-      const double pobj = usc<ICE>(acc[6] + c0), dobj = usc<ICE>(acc[7] + acc[8] + c0);
-      const double pres = usc<ICE>(sqrt(acc[4]) / (1.0 + sgpr_fresh<ICE>(qnorm)));
-      const double dres = usc<ICE>(sqrt(acc[5]) / (1.0 + sgpr_fresh<ICE>(cnorm)));
-      const double gap = usc<ICE>(fabs(pobj - dobj) / (1.0 + fabs(pobj) + fabs(dobj)));
+      const double pobj = usc<USC>(acc[6] + c0), dobj = usc<USC>(acc[7] + acc[8] + c0);
+      const double pres = usc<USC>(sqrt(acc[4]) / (1.0 + sgpr_fresh<USC>(qnorm)));
+      const double dres = usc<USC>(sqrt(acc[5]) / (1.0 + sgpr_fresh<USC>(cnorm)));
+      const double gap = usc<USC>(fabs(pobj - dobj) / (1.0 + fabs(pobj) + fabs(dobj)));
       if (tid == 0) {
         fin[0] = pobj;
         fin[1] = pres;
@@ -1377,7 +1413,7 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
       }
       if constexpr (GATE) {
         gate.note(pres, dres, gap, o.eps, r);
-        gate.q = usc<ICE>(gate.q);
+        gate.q = usc<USC>(gate.q);
       }
       if (!(isfinite(pobj) && isfinite(dobj))) {
         status = kNumerical;
