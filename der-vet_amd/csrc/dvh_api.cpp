@@ -238,6 +238,12 @@ int dvh_last_path_counts(const dvh_handle* h, int32_t* out3) { return path_count
 int dvh_last_path_counts4(const dvh_handle* h, int32_t* out4) { return path_counts(h, out4, 4); }
 int dvh_last_path_counts5(const dvh_handle* h, int32_t* out5) { return path_counts(h, out5, 5); }
 
+int dvh_last_band_variant(const dvh_handle* h, int32_t* out) {
+  if (!h || !out) return DVH_ERR_ARG;
+  *out = h->last_band_variant;
+  return DVH_OK;
+}
+
 int dvh_last_chain_aborts(const dvh_handle* h, int32_t* out) {
   if (!h || !out) return DVH_ERR_ARG;
   *out = h->st.n_chain_aborts;

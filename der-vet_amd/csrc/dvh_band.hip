@@ -21,7 +21,8 @@
 // per-lane partials.  Three forms are instantiated (launch_pdhg_band, at the end of the file):
 //   <256, 3> battery  three steps per lane, 4 waves = one per SIMD, about 252 VGPRs (2 waves per SIMD), costs and
 //                     right-hand sides in LDS: two windows share a CU, so one window's barrier waits are filled by the
-//                     other's work.  The default; persistent grid (dvh_band_persist.hip).
+//                     other's work.  The default; persistent grid (dvh_band_persist.hip), which also has the form's
+//                     single-demand-period instantiation (band_window, J1) for lists whose windows all have J == 1.
 //   <768, 1> battery  one step per lane, 12 waves, one window per CU: batches of at most one window per CU
 //                     (dvh_api.cpp picks the form by batch size), one workgroup per window.
 //   <768, 1> ICE      one step per lane at a 168-VGPR budget (3 waves per SIMD; twice the per-step state, the ICE
@@ -39,7 +40,7 @@ namespace dvh {
 namespace {
 
 constexpr int kBandSteps = 768;  // steps per window (T <= kBandSteps)
-constexpr int kJMax = 4;         // tau (demand-period) columns per window
+constexpr int kJMax = kBandJMax;  // tau (demand-period) columns per window
 constexpr int kNeedsEll = -2;
 
 // LDS layout (B lanes, S steps per lane, SB = S B steps; NC / NR = columns / rows per step), doubles then ints:
@@ -199,7 +200,13 @@ __device__ __forceinline__ double sgpr_fresh(double v) {
   if constexpr (USC) asm volatile("" : "+s"(v));
   return v;
 }
-template <int B, int S, bool ICE, bool LC, int WPS, bool GATE, bool BOX>
+// J1: the single-demand-period instantiation (three-step battery form): J is the constant 1 through the whole window, so
+// the set-up's, the checks' and the write-back's loops over the tau columns are straight-line code, and the waves
+// without the tau column (wave 0 is the tau wave of every window) carry no tau update, no init row, no period index per
+// step and read XT[0] once per dual half-step.  The arithmetic and its order are those of the run-time J == 1 path.  The
+// host launches it only for lists without a J != 1 battery window (launch_pdhg_band, j1); a window whose descriptor
+// says otherwise leaves through bail() with the first test, before any shared state is written.
+template <int B, int S, bool ICE, bool LC, int WPS, bool GATE, bool BOX, bool J1 = false>
 __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const Chunk& ch, const Opts& o, const int k_in,
                                             const int tid) {
   // the window index and its descriptor's offsets through v_readfirstlane, so that they and every address formed from
@@ -219,7 +226,8 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
   const int n = W.n, m = W.m, meq = W.meq;
   const int lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   double* scal = w.scal + (int64_t)kl * kScal;
-  const int T = meq - 1, J = n - (ICE ? 5 : 3) * T, MI = m - meq;
+  static_assert(!(J1 && ICE), "the single-demand-period instantiation is a battery form");
+  const int T = meq - 1, JD = n - (ICE ? 5 : 3) * T, J = J1 ? 1 : JD, MI = m - meq;
   const int MD = ICE ? MI - 2 * T : MI;  // DCM rows
   auto bail = [&]() {
     if (tid == 0) {
@@ -229,8 +237,8 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
   };
   // the kernel scales its windows itself (below): it runs before, and instead of, setup_kernel, whose outputs it
   // does not read; the windows it hands on are set up after it (dvh_api.cpp device_cascade)
-  if (n > kSmallMax || m > kSmallMax || T < 1 || T > SB || J < 0 || J > kJMax || MD < 0 || MD > T ||
-      (J == 0 && MD > 0)) {
+  if (n > kSmallMax || m > kSmallMax || T < 1 || T > SB || JD < 0 || JD > kJMax || MD < 0 || MD > T ||
+      (JD == 0 && MD > 0) || (J1 && JD != 1)) {
     bail();
     return;
   }
@@ -455,7 +463,7 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
     if (dv >= 0) {
       drow[s] = dv >> 3;
       DRL[s * B + tid] = drow[s];
-      jt[s] = dv & 7;
+      jt[s] = J1 ? 0 : dv & 7;
       for (int p = gkp[drow[s]]; p < gkp[drow[s] + 1]; ++p) {
         const int c = gkc[p];
         const double a = gkv[p];
@@ -1144,8 +1152,14 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
       // issued together, one wait instead of one per read
       const double xen = XE[tid + 1];
       double xtv[S];
+      if constexpr (J1) {  // one tau column: one read
+        const double xt0 = XT[0];
 #pragma unroll
-      for (int s = 0; s < S; ++s) xtv[s] = lds_ld(xta[s]);
+        for (int s = 0; s < S; ++s) xtv[s] = xt0;
+      } else {
+#pragma unroll
+        for (int s = 0; s < S; ++s) xtv[s] = lds_ld(xta[s]);
+      }
       kfin_next(S - 1, kx[S - 1], xen);
       // the >= rows first: their duals feed the tau partials, whose wave reduction then has the SOE rows' work
       // beside it
@@ -1159,7 +1173,7 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
 #pragma unroll
       for (int s = !W0 ? S - 1 : 0; s < S; ++s) row_step(s, 0);  // (the lane-local SOE rows: see below)
       YS[tid + 1] = y[S - 1][0];
-      if (W0 || wid == 0) {  // init row (lane kInitLane): ene_0 = target
+      if (W0 || (!J1 && wid == 0)) {  // init row (lane kInitLane): ene_0 = target; (J1: wave 0 is always W0)
         if (ilane) {
           const double y0 = sp[0], ya0 = sp[1];
           const double q1 = fma(sigma, sp[3] - sp[4] * XE[0], y0);
@@ -1225,6 +1239,11 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
   // between the two, and what their lane masks skip, holds no barrier) -- the waves of a workgroup, some in one loop and
   // some in the other, meet at every barrier.  (The two traps of the persistent loop below apply here as well: a
   // lane-dependent trip count would be structurized into a loop whose barriers the waves do not reach in step.)
+  // The single-demand-period instantiation (J1) keeps all of this: it adds no loop and changes no trip count (np is formed
+  // as before), w0 is then wid == 0, a scalar, so each wave still takes one of the same two loops, and what J1 takes
+  // out of the other waves' body -- the J > 1 tau update, the init row, the per-step XT reads -- are lane-masked blocks
+  // and LDS reads without a barrier: both bodies still pass both barriers once per trip, and the other waves' body
+  // becomes an innermost loop without the two child loops over the tau columns (profiles/band_j1_shape.txt).
   while (it < o.max_iters) {
     if constexpr (Tune::plain_loop) {
       if (ck > 1) {  // the ck - 1 plain iterations up to the next check, or those left to max_iters
@@ -1562,6 +1581,35 @@ __global__ __launch_bounds__(B, WPS) void pdhg_band_kernel(const BandArgs args) 
   }
 }
 
+// The single-demand-period instantiation (band_window, J1) of the persistent form: pdhg_band_kernel's persistent loop
+// again, statement for statement (its comments hold here too), in a kernel of its own name and text.  (One body inlined
+// into both kernels changed the machine code of every other form, the ICE form's included, and a further template
+// parameter their symbols.)
+template <int B, int S, bool ICE, bool LC, int WPS, bool GATE, bool BOX>
+__global__ __launch_bounds__(B, WPS) void pdhg_band_kernel_j1(const BandArgs args) {
+  __shared__ int32_t next;
+  for (;;) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    using KArgs = const __attribute__((address_space(4))) BandArgs*;
+    KArgs kp = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(kp));
+    const BandArgs& args = *(const BandArgs*)kp;
+#endif
+    if (__builtin_amdgcn_readfirstlane(threadIdx.x) < kWave)
+      next = __builtin_amdgcn_readfirstlane(atomicAdd(args.queue, (threadIdx.x & (kWave - 1)) == 0 ? 1 : 0));
+    __syncthreads();
+    const int i = __builtin_amdgcn_readfirstlane(next);
+    __syncthreads();
+    if (i >= args.count) return;
+    int tid = threadIdx.x;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(tid));
+#endif
+    band_window<B, S, ICE, LC, WPS, GATE, BOX, true>(args.b, args.w, args.ch, args.o,
+                                                     args.list ? args.list[i] : args.ch.first + i, tid);
+  }
+}
+
 template <int B, int S, bool ICE, bool LC, int WPS, bool GATE, bool BOX, bool PERSIST>
 hipError_t launch_band_one_q(const Batch& b, const Work& w, const Chunk& ch, const Opts& o, hipStream_t s,
                              const int32_t* list, int nlist, int* variant_out) {
@@ -1609,11 +1657,11 @@ hipError_t launch_band_one_q(const Batch& b, const Work& w, const Chunk& ch, con
 }
 template <int B, int S, bool ICE, bool LC, int WPS, bool GATE, bool BOX>
 hipError_t launch_band_one_g(const Batch& b, const Work& w, const Chunk& ch, const Opts& o, hipStream_t s,
-                             const int32_t* list, int nlist, int* variant_out) {
+                             const int32_t* list, int nlist, bool j1, int* variant_out) {
   if constexpr (S == 3 && !ICE) {  // the persistent form (DVH_BAND_QUEUE=0: one workgroup per window, A/B)
     static_assert(B == kBandSteps / 3 && LC && WPS == 2, "dvh_band_persist.hip instantiates this form");
     const char* q = getenv("DVH_BAND_QUEUE");
-    if (!(q && atoi(q) == 0)) return launch_band_persist(GATE, BOX, b, w, ch, o, s, list, nlist, variant_out);
+    if (!(q && atoi(q) == 0)) return launch_band_persist(GATE, BOX, j1, b, w, ch, o, s, list, nlist, variant_out);
   }
   if constexpr (ICE) {  // the ICE form's persistent grid (DVH_BAND_QUEUE=0 or DVH_BAND_QUEUE_ICE=0: off, A/B)
     static_assert(B == kBandSteps && S == 1 && !LC && WPS == 3, "dvh_band_persist_ice.hip instantiates this form");
@@ -1626,10 +1674,10 @@ hipError_t launch_band_one_g(const Batch& b, const Work& w, const Chunk& ch, con
 }
 template <int B, int S, bool ICE, bool LC, int WPS, bool BOX = false>
 hipError_t launch_band_one(const Batch& b, const Work& w, const Chunk& ch, const Opts& o, hipStream_t s,
-                           const int32_t* list, int nlist, int* variant_out) {
+                           const int32_t* list, int nlist, bool j1, int* variant_out) {
   if (o.kkt_predict > 0)
-    return launch_band_one_g<B, S, ICE, LC, WPS, true, BOX>(b, w, ch, o, s, list, nlist, variant_out);
-  return launch_band_one_g<B, S, ICE, LC, WPS, false, BOX>(b, w, ch, o, s, list, nlist, variant_out);
+    return launch_band_one_g<B, S, ICE, LC, WPS, true, BOX>(b, w, ch, o, s, list, nlist, j1, variant_out);
+  return launch_band_one_g<B, S, ICE, LC, WPS, false, BOX>(b, w, ch, o, s, list, nlist, j1, variant_out);
 }
 
 }  // namespace
@@ -1645,9 +1693,54 @@ hipError_t launch_band_one(const Batch& b, const Work& w, const Chunk& ch, const
 // across every window's iterations (56 spilled dwords, 12.6 % slower per iteration than one workgroup per window at
 // equal durations; 1.6 % without the hoisting, profiles/r04al_band_persist_nolicm.log).  The one-workgroup forms keep
 // the hoisting (this build of them is 1.4 % slower per iteration).
-hipError_t launch_band_persist(bool gate, bool box, const Batch& b, const Work& w, const Chunk& ch, const Opts& o,
-                               hipStream_t s, const int32_t* list, int nlist, int* variant_out) {
+namespace {
+// The single-demand-period instantiation's launch: launch_band_one_q's persistent grid (the resident slots measured for
+// this kernel, DVH_BAND_RESERVE, the zeroed queue counter) over pdhg_band_kernel_j1, reported as the form's variant
+// code + kBandJ1.  (A launcher of its own, so that the ICE unit, which shares launch_band_one_q, is built as before.)
+template <bool GATE, bool BOX>
+hipError_t launch_band_persist_j1(const Batch& b, const Work& w, const Chunk& ch, const Opts& o, hipStream_t s,
+                                  const int32_t* list, int nlist, int* variant_out) {
+  constexpr int B = kBandSteps / 3, S = 3;
+  const size_t lds = band_lds_bytes(B, S, false, true);
+  auto kern = pdhg_band_kernel_j1<B, S, false, true, 2, GATE, BOX>;
+  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  const int count = list ? nlist : ch.count;
+  if (count <= 0) return hipSuccess;
+  int& slots = w.slots[8 + (GATE ? 2 : 0) + (BOX ? 1 : 0)];
+  if (slots <= 0) {
+    int nb = 0, cus = 0, dev = 0;
+    if ((e = hipGetDevice(&dev)) != hipSuccess) return e;
+    if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)kern, B, lds)) != hipSuccess) return e;
+    if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
+    slots = std::max(1, nb) * std::max(1, cus);
+  }
+  static const int reserve = [] { const char* e = getenv("DVH_BAND_RESERVE"); return e ? std::max(0, atoi(e)) : 0; }();
+  const int grid = std::min(count, std::max(1, slots - 2 * reserve));
+  if ((e = hipMemsetAsync(w.queue, 0, sizeof(int32_t), s)) != hipSuccess) return e;
+  const BandArgs args{b, w, ch, o, list, count, w.queue};
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(B), lds, s, args);
+  if (variant_out) *variant_out = 9000000 + 1000 * (S - 1) + kBandJ1 + B / kWave;
+  return hipGetLastError();
+}
+}  // namespace
+// j1: the list holds no battery window with J != 1 (counted by the host from the descriptors, dvh_solve.cpp
+// scan_chunks): the single-demand-period instantiation takes it, unless DVH_BAND_J1=0 (read at every launch, A/B)
+hipError_t launch_band_persist(bool gate, bool box, bool j1, const Batch& b, const Work& w, const Chunk& ch,
+                               const Opts& o, hipStream_t s, const int32_t* list, int nlist, int* variant_out) {
   constexpr int B = kBandSteps / 3;
+  if (j1) {
+    const char* e = getenv("DVH_BAND_J1");
+    if (e && atoi(e) == 0) j1 = false;
+  }
+  if (j1) {
+    if (gate) {
+      if (box) return launch_band_persist_j1<true, true>(b, w, ch, o, s, list, nlist, variant_out);
+      return launch_band_persist_j1<true, false>(b, w, ch, o, s, list, nlist, variant_out);
+    }
+    if (box) return launch_band_persist_j1<false, true>(b, w, ch, o, s, list, nlist, variant_out);
+    return launch_band_persist_j1<false, false>(b, w, ch, o, s, list, nlist, variant_out);
+  }
   if (gate) {
     if (box) return launch_band_one_q<B, 3, false, true, 2, true, true, true>(b, w, ch, o, s, list, nlist, variant_out);
     return launch_band_one_q<B, 3, false, true, 2, true, false, true>(b, w, ch, o, s, list, nlist, variant_out);
@@ -1668,17 +1761,17 @@ hipError_t launch_band_persist_ice(bool gate, bool box, const Batch& b, const Wo
 }
 #else
 hipError_t launch_pdhg_band(const Batch& b, const Work& w, const Chunk& ch, const Opts& o, hipStream_t s, bool ice,
-                            int form, bool box, const int32_t* list, int nlist, int* variant_out) {
+                            int form, bool box, const int32_t* list, int nlist, bool j1, int* variant_out) {
   if (ice) {
-    if (box) return launch_band_one<kBandSteps, 1, true, false, 3, true>(b, w, ch, o, s, list, nlist, variant_out);
-    return launch_band_one<kBandSteps, 1, true, false, 3>(b, w, ch, o, s, list, nlist, variant_out);
+    if (box) return launch_band_one<kBandSteps, 1, true, false, 3, true>(b, w, ch, o, s, list, nlist, false, variant_out);
+    return launch_band_one<kBandSteps, 1, true, false, 3>(b, w, ch, o, s, list, nlist, false, variant_out);
   }
-  if (form == 1) {
-    if (box) return launch_band_one<kBandSteps, 1, false, false, 3, true>(b, w, ch, o, s, list, nlist, variant_out);
-    return launch_band_one<kBandSteps, 1, false, false, 3>(b, w, ch, o, s, list, nlist, variant_out);
+  if (form == 1) {  // (the one-step form has no single-demand-period instantiation)
+    if (box) return launch_band_one<kBandSteps, 1, false, false, 3, true>(b, w, ch, o, s, list, nlist, false, variant_out);
+    return launch_band_one<kBandSteps, 1, false, false, 3>(b, w, ch, o, s, list, nlist, false, variant_out);
   }
-  if (box) return launch_band_one<kBandSteps / 3, 3, false, true, 2, true>(b, w, ch, o, s, list, nlist, variant_out);
-  return launch_band_one<kBandSteps / 3, 3, false, true, 2>(b, w, ch, o, s, list, nlist, variant_out);
+  if (box) return launch_band_one<kBandSteps / 3, 3, false, true, 2, true>(b, w, ch, o, s, list, nlist, j1, variant_out);
+  return launch_band_one<kBandSteps / 3, 3, false, true, 2>(b, w, ch, o, s, list, nlist, j1, variant_out);
 }
 #endif
 

@@ -161,8 +161,12 @@ int chain_pass(dvh_handle* h, const dvh::Batch& b, const dvh::Work& w, const dvh
 // One small read-back per stage that ran ({count, ELL widths, max n / m / nnz} of the windows it hands on; two after
 // the ICE form when it refuses windows: their count, then their size classes once they are set up); a batch the band
 // kernel takes whole waits once.
+// nj: the chunk's battery-shaped windows with J != 1 demand periods, counted by the host from the descriptors it
+// holds anyway (scan_chunks; the first band launch precedes every routing pass, so no device count could reach it
+// without a wait of its own): 0 lets the three-step battery form run its single-demand-period instantiation, over the
+// chunk and over any list taken from it; anything else keeps the generic instantiation for all of them.
 int device_cascade(dvh_handle* h, const dvh::Batch& b, const dvh::Work& w, const dvh::Chunk& ch, const dvh::Opts& o,
-                   int nsmall, int wc, int mn, int mm, hipStream_t s, const int32_t* order) {
+                   int nsmall, int nj, int wc, int mn, int mm, hipStream_t s, const int32_t* order) {
   const size_t I = sizeof(int32_t);
   int32_t* L[5];
   for (int r = 0; r < 5; ++r) L[r] = h->d_list.as<int32_t>() + (size_t)r * wc;
@@ -183,7 +187,12 @@ int device_cascade(dvh_handle* h, const dvh::Batch& b, const dvh::Work& w, const
     hipError_t e = hipMemcpyAsync(rh + 8 * slot0, info + 8 * slot0, 8 * I * nslots, hipMemcpyDeviceToHost, s);
     return e != hipSuccess ? e : sync_stream(h, s);
   };
+  const bool j1 = nj == 0;
   int variant = -1, bvar = -1;
+  h->last_band_variant = -1;
+  // the form's code without the instantiation's (dvh_last_stats reports one code per form, dvh_last_band_variant the
+  // instantiation that ran)
+  auto form_code = [](int v) { return v >= 0 && v % 100 >= dvh::kBandJ1 ? v - dvh::kBandJ1 : v; };
   // the battery forms iterate on [0, 1]-normalised boxes (dvh_band.hip BOX; bench 246.4k vs 239.7k windows/s,
   // profiles/r04m_ab_band_box.log); the few windows with an unbounded ch / dis / ene column (status -3) are re-run by
   // the plain form, which takes every one of them (same structure and scaling checks), after the same read-back.
@@ -193,7 +202,7 @@ int device_cascade(dvh_handle* h, const dvh::Batch& b, const dvh::Work& w, const
   const int box_mode = box_env ? atoi(box_env) : 1;
   const bool box = box_mode >= 1, box_ice = box_mode >= 2;
   // (order: the chunk's windows in the caller's launch order, dvh_set_launch_order; the results do not depend on it)
-  DVH_HIP(h, dvh::launch_pdhg_band(b, w, ch, o, s, false, form_for(ch.count), box, order, order ? ch.count : 0, &bvar));
+  DVH_HIP(h, dvh::launch_pdhg_band(b, w, ch, o, s, false, form_for(ch.count), box, order, order ? ch.count : 0, j1, &bvar));
   DVH_HIP(h, route(0, nullptr, ch.count, -2, 0, 0));
   if (box) DVH_HIP(h, route(1, nullptr, ch.count, -3, 0, 1));
   DVH_HIP(h, readback(0, box ? 2 : 1));
@@ -201,15 +210,18 @@ int device_cascade(dvh_handle* h, const dvh::Batch& b, const dvh::Work& w, const
     // the plain form over the windows without a box; it can refuse some of them itself (-2: factors outside float's
     // range, checked after scaling, which the box form never reached for them), so the -2 list is formed again, over
     // the chunk, once it has run -- one more read-back, only when such windows exist
-    DVH_HIP(h, dvh::launch_pdhg_band(b, w, ch, o, s, false, form_for(rh[8]), false, L[1], rh[8], nullptr));
+    DVH_HIP(h, dvh::launch_pdhg_band(b, w, ch, o, s, false, form_for(rh[8]), false, L[1], rh[8], j1, nullptr));
     DVH_HIP(h, route(0, nullptr, ch.count, -2, 0, 0));
     DVH_HIP(h, readback(0, 1));
   }
   int cur = rh[0];
   h->st.n_band += nsmall - cur;
-  if (nsmall - cur > 0) variant = bvar;
+  if (nsmall - cur > 0) {
+    variant = form_code(bvar);
+    h->last_band_variant = bvar;
+  }
   if (cur > 0) {  // pass 2: the band kernel's ICE form over pass 1's refusals
-    DVH_HIP(h, dvh::launch_pdhg_band(b, w, ch, o, s, true, form_for(cur), box_ice, L[0], cur, &bvar));
+    DVH_HIP(h, dvh::launch_pdhg_band(b, w, ch, o, s, true, form_for(cur), box_ice, L[0], cur, false, &bvar));
     // dvh_set_kernel_path 5: the interconnection form (dvh_band_grid.hip) over the same list, behind the ICE form on
     // the stream: its workgroups leave at once unless their window is still refused (-2), so the route below sees the
     // final statuses and the mode adds no read-back.  (Which of the two forms took the pass's windows is not read
@@ -219,7 +231,7 @@ int device_cascade(dvh_handle* h, const dvh::Batch& b, const dvh::Work& w, const
     if (box_ice) DVH_HIP(h, route(2, L[0], cur, -3, 0, 1));
     DVH_HIP(h, readback(1, box_ice ? 2 : 1));
     if (box_ice && rh[16] > 0) {  // the plain ICE form over the ICE windows without a box; its -2s listed again
-      DVH_HIP(h, dvh::launch_pdhg_band(b, w, ch, o, s, true, form_for(rh[16]), false, L[1], rh[16], nullptr));
+      DVH_HIP(h, dvh::launch_pdhg_band(b, w, ch, o, s, true, form_for(rh[16]), false, L[1], rh[16], false, nullptr));
       DVH_HIP(h, route(1, L[0], cur, -2, 0, 4));
       DVH_HIP(h, readback(1, 1));
     }

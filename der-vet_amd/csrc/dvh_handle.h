@@ -85,6 +85,7 @@ struct dvh_handle : dvh_handle_core {
   int n_syncs = 0;                                // host waits on the stream in the last solve
   double outage_ms = 0.0;
   int last_variant = -1;
+  int last_band_variant = -1;  // the battery band pass's instantiation code (dvh_last_band_variant), -1: it took nothing
   int kernel_path = 0;  // 0 band -> ELL -> generic, 1 generic only, 2 ELL -> generic (no band kernel), 3 / 4 as 0
                         // with the battery band kernel's one-step / three-step form forced (0 picks by batch size),
                         // 5 as 0 plus the band kernel's interconnection form
@@ -123,7 +124,7 @@ inline int hip_fail(dvh_handle* h, hipError_t e, const char* where) {
 namespace dvh {
 
 // The tier drivers of one chunk (dvh_cascade.cpp), called by solve_packed (dvh_solve.cpp).
-int device_cascade(dvh_handle* h, const Batch& b, const Work& w, const Chunk& ch, const Opts& o, int nsmall, int wc,
+int device_cascade(dvh_handle* h, const Batch& b, const Work& w, const Chunk& ch, const Opts& o, int nsmall, int nj, int wc,
                    int mn, int mm, hipStream_t s, const int32_t* order);
 int chain_pass(dvh_handle* h, const Batch& b, const Work& w, const Chunk& ch, const Opts& o,
                const std::vector<int32_t>& med, int max_T, const std::vector<int64_t>& desc,

@@ -99,7 +99,7 @@ struct Work {
                     //   device (0: not measured yet); per handle, so that handles of a multi-device handle, driven
                     //   by their own host threads, never share it
 };
-constexpr int kPersistForms = 8;  // (ICE, GATE, BOX) of the persistent band kernels
+constexpr int kPersistForms = 12;  // (ICE, GATE, BOX) of the persistent band kernels, then (GATE, BOX) of the J1 ones
 
 struct Chunk {
   int first;        // first window index (global)
@@ -127,15 +127,20 @@ hipError_t launch_pdhg_ell(const Batch& b, const Work& w, const Chunk& ch, const
 // window shape come back with istats status -2 (kNeedsEll) and must be re-run by launch_pdhg_ell.
 // ice: the variant with LP-relaxed ICE columns (elec, on) and rows; list (nlist entries): global window indices,
 // or null for the whole chunk; form: steps per lane of the battery kernel (3 default, 1 = the 768-thread form);
-// variant_out: 9000000 + 1000 (steps per lane - 1) + 100 ice + waves per window.
+// variant_out: 9000000 + 1000 (steps per lane - 1) + 100 ice + waves per window (+ kBandJ1: the three-step form's
+// single-demand-period instantiation).
+// j1: no window of the list (or chunk) is a battery window with J != 1 demand periods, so the persistent three-step
+// form may take its single-demand-period instantiation (J a compile-time 1); the other forms ignore it.
 // box (battery forms): iterate on the columns' [0, 1]-normalised boxes (dvh_band.hip, BOX); windows with an unbounded
 // ch / dis / ene column come back with status -3 (kNeedsPlain) and must be re-run with box = false.
 hipError_t launch_pdhg_band(const Batch& b, const Work& w, const Chunk& ch, const Opts& o, hipStream_t s, bool ice,
-                            int form, bool box, const int32_t* list, int nlist, int* variant_out);
+                            int form, bool box, const int32_t* list, int nlist, bool j1, int* variant_out);
+constexpr int kBandJ1 = 50;
+constexpr int kBandJMax = 4;  // tau (demand-period) columns per band window
 // Its persistent forms (dvh_band_persist.hip), the default for the three-step battery form and the ICE form unless
 // DVH_BAND_QUEUE=0 (DVH_BAND_QUEUE_ICE=0: the ICE form only); gate: dvh_options.kkt_predict > 0.
-hipError_t launch_band_persist(bool gate, bool box, const Batch& b, const Work& w, const Chunk& ch, const Opts& o,
-                               hipStream_t s, const int32_t* list, int nlist, int* variant_out);
+hipError_t launch_band_persist(bool gate, bool box, bool j1, const Batch& b, const Work& w, const Chunk& ch,
+                               const Opts& o, hipStream_t s, const int32_t* list, int nlist, int* variant_out);
 hipError_t launch_band_persist_ice(bool gate, bool box, const Batch& b, const Work& w, const Chunk& ch, const Opts& o,
                                    hipStream_t s, const int32_t* list, int nlist, int* variant_out);
 size_t setup_lds_bytes(int max_n, int max_m);

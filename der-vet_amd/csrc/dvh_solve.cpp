@@ -98,6 +98,7 @@ struct ChunkPlan {
   int mn, mm;
   int64_t mnz;
   int nsmall;
+  int nj;  // small windows of battery shape with J != 1 demand periods (device_cascade: the band kernel's instantiation)
   std::vector<int32_t> med;
   int med_T = 0;
 };
@@ -139,6 +140,10 @@ BatchPlan scan_chunks(const std::vector<int64_t>& desc, int count, bool chain_on
         continue;
       }
       ++c.nsmall;
+      // n = 3 T + J, T = m_eq - 1: J = 0, 2 .. kJMax are the battery windows the single-demand-period instantiation of
+      // the band kernel must not get (every other J != 1 is no battery window: both instantiations refuse it alike)
+      const int64_t J = d[0] - 3 * (d[2] - 1);
+      if (J == 0 || (J >= 2 && J <= dvh::kBandJMax)) ++c.nj;
       c.mn = std::max<int>(c.mn, (int)d[0]);
       c.mm = std::max<int>(c.mm, (int)d[1]);
       c.mnz = std::max(c.mnz, d[3]);
@@ -309,7 +314,7 @@ int solve_packed(dvh_handle* h, const dvh_packed* bt, const std::vector<int64_t>
     if (c.nsmall > 0 && !cascade) DVH_HIP(h, dvh::launch_setup(b, w, c.ch, o, c.mn, c.mm, s));
     DVH_HIP(h, hipEventRecord(ce[1], s));
     if (c.nsmall > 0)
-      if (int rc = cascade ? dvh::device_cascade(h, b, w, c.ch, o, c.nsmall, plan.wc, c.mn, c.mm, s, order)
+      if (int rc = cascade ? dvh::device_cascade(h, b, w, c.ch, o, c.nsmall, c.nj, plan.wc, c.mn, c.mm, s, order)
                            : host_list_tiers(h, b, w, c, o, fast, desc, s))
         return rc;
     if (int rc = dvh::chain_pass(h, b, w, c.ch, o, c.med, c.med_T, desc, med_done, s)) return rc;

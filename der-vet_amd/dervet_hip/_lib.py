@@ -173,6 +173,7 @@ SYMBOLS = {
     "dvh_last_path_counts": (ctypes.c_int, [ctypes.c_void_p, c_int32_p]),
     "dvh_last_path_counts4": (ctypes.c_int, [ctypes.c_void_p, c_int32_p]),
     "dvh_last_path_counts5": (ctypes.c_int, [ctypes.c_void_p, c_int32_p]),
+    "dvh_last_band_variant": (ctypes.c_int, [ctypes.c_void_p, c_int32_p]),
     "dvh_last_chain_aborts": (ctypes.c_int, [ctypes.c_void_p, c_int32_p]),
     "dvh_last_warning": (ctypes.c_char_p, [ctypes.c_void_p]),
     "dvh_set_kernel_path": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),

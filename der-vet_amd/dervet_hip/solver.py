@@ -147,9 +147,14 @@ class BatchSolver:
         self._check(self._lib.dvh_last_path_counts5(self._h, c), "dvh_last_path_counts5")
         a = ctypes.c_int32()
         self._check(self._lib.dvh_last_chain_aborts(self._h, ctypes.byref(a)), "dvh_last_chain_aborts")
-        return {"band_windows": c[3], "ell_windows": v[0], "generic_windows": v[1], "variant": v[2],
-                "generic_only": bool(v[3]), "large_windows": c[2], "chain_windows": c[4],
-                "chain_aborts": int(a.value)}
+        out = {"band_windows": c[3], "ell_windows": v[0], "generic_windows": v[1], "variant": v[2],
+               "generic_only": bool(v[3]), "large_windows": c[2], "chain_windows": c[4],
+               "chain_aborts": int(a.value)}
+        if hasattr(self._lib, "dvh_last_band_variant"):  # (an A/B build of an earlier library has none)
+            bv = ctypes.c_int32()
+            self._check(self._lib.dvh_last_band_variant(self._h, ctypes.byref(bv)), "dvh_last_band_variant")
+            out["band_variant"] = int(bv.value)
+        return out
 
     def last_warning(self):
         """Diagnostics of the last solve's fallbacks (a medium-tier team launch that aborted), or ''."""

@@ -342,6 +342,10 @@ int dvh_last_path_counts4(const dvh_handle* h, int32_t* out4);
  * 769 .. 12,288 steps -- the annual hourly window n = "year", sub-hourly monthly windows -- solved as a batch, a
  * team of one workgroup per <= 768-step segment per window, dvh_chain.hip)}. */
 int dvh_last_path_counts5(const dvh_handle* h, int32_t* out5);
+/* The instantiation of the battery-banded kernel that the most recent solve's battery pass ran: the kernel variant code
+ * of dvh_last_stats, + 50 where the three-step form ran with the demand-period count fixed at 1 (no window of the
+ * chunk had another; DVH_BAND_J1=0 in the environment keeps the run-time count); -1 where the pass took no window. */
+int dvh_last_band_variant(const dvh_handle* h, int32_t* out);
 /* Medium-tier team launches of the most recent solve that aborted (a segment exchange outlasted the spin limit): the
  * windows such a launch had finished keep their results, the others were solved on the grid-wide path, and the solve
  * still returns DVH_OK.  out = that count (0 when nothing aborted); reset by every solve. */

@@ -56,7 +56,7 @@ def main():
     from bench import source_key  # noqa: E402
     res = {
         "source_key": source_key(),
-        "kernel": re.search(r"pdhg_(band|ell)_kernel<[^>]*>", kern[0]).group(0),
+        "kernel": re.search(r"pdhg_(band|ell)_kernel\w*<[^>]*>", kern[0]).group(0),
         "windows": windows,
         "dispatches_fetch": len(fv), "dispatches_write": len(wv),
         "fetch_size_kb_raw": f_kb, "write_size_kb": w_kb,
