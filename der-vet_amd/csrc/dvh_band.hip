@@ -1493,9 +1493,9 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
         const double d = dcf(j), lo = lraw[j] / d, hv = uraw[j] / d;
         double wv = hv - (v == 2 ? lo : 0.0);  // the set-up's width, by the set-up's operations
         if (!(wv >= 0x1p-500)) wv = 0.0;
-        xo_g[j] = fmin(fmax(fma(wv, xpi(v, s), lo), lo), hv) * d;
+        xo_g[j] = unscale_x(fmin(fmax(fma(wv, xpi(v, s), lo), lo), hv), d, lraw[j], uraw[j]);
       } else {
-        xo_g[j] = xpi(v, s) * dcf(j);
+        xo_g[j] = unscale_x(xpi(v, s), dcf(j), lraw[j], uraw[j]);
       }
     }
     yo_g[t + 1] = ypi(0, s) * drf(t + 1);
@@ -1506,7 +1506,7 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
       yo_g[rb[s]] = ypi(3, s) * drf(rb[s]);
     }
   }
-  if (tlane) xo_g[3 * T + lane] = sp[5] * dcf(3 * T + lane);
+  if (tlane) xo_g[3 * T + lane] = unscale_x(sp[5], dcf(3 * T + lane), lraw[3 * T + lane], uraw[3 * T + lane]);
   if (ilane) yo_g[0] = sp[2] * drf(0);
   if constexpr (DVH_BAND_PROBE) {
     pstamp(4);

@@ -886,7 +886,7 @@ __device__ __forceinline__ void grid_window(const Batch& b, const Work& w, const
     for (int v = 0; v < NC; ++v) {
       if (v == 3 && !PV) continue;
       const int j = col(v);
-      xo_g[j] = xpi(v) * dcv[j];
+      xo_g[j] = unscale_x(xpi(v), dcv[j], lraw[j], uraw[j]);
     }
 #pragma unroll
     for (int r = 0; r < NR; ++r) {
@@ -894,7 +894,7 @@ __device__ __forceinline__ void grid_window(const Batch& b, const Work& w, const
       if (i >= 0) yo_g[i] = ypi(r) * drv[i];
     }
   }
-  if (tlane) xo_g[3 * T + lane] = sp[5] * dcv[3 * T + lane];
+  if (tlane) xo_g[3 * T + lane] = unscale_x(sp[5], dcv[3 * T + lane], lraw[3 * T + lane], uraw[3 * T + lane]);
   if (ilane) yo_g[0] = sp[2] * drv[0];
   if (tid == 0) {
     b.istats[2 * k] = status;

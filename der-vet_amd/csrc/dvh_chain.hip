@@ -1454,11 +1454,15 @@ __global__ __launch_bounds__(kCB, 3) void pdhg_chain_kernel(const Batch b, const
     // outputs: the last check's T(z_k), unscaled
     if (val) {
 #pragma unroll
-      for (int v = 0; v < NC; ++v) xo_g[col(v)] = XP[v * B + tid] * dcv[col(v)];
+      for (int v = 0; v < NC; ++v) {
+        const int j = col(v);
+        xo_g[j] = unscale_x(XP[v * B + tid], dcv[j], b.l[W.on + j], b.u[W.on + j]);
+      }
       yo_g[t + 1] = YP[tid] * drv[t + 1];
       if (drow >= 0) yo_g[drow] = YP[B + tid] * drv[drow];
     }
-    if (tlane && town) xo_g[3 * T + jg0] = sp[5] * dcv[3 * T + jg0];
+    if (tlane && town)
+      xo_g[3 * T + jg0] = unscale_x(sp[5], dcv[3 * T + jg0], b.l[W.on + 3 * T + jg0], b.u[W.on + 3 * T + jg0]);
     if (ilane) yo_g[0] = sp[2] * drv[0];
 #ifdef DVH_CHAIN_PROBE_TIMING
     if (tid == kTauWave * kWave) abort_word[16 + 8 * (int)blockIdx.x + 6] = (int)t_probe[0];

@@ -40,6 +40,15 @@ constexpr int kPlanInts = kPlanHi + kChainJSeg * kPMax;
 // n + 1 transpose cursors in LDS
 constexpr int kMedSetupNMax = 40000;
 
+// A column's output value: the scaled x~ times its factor d, clipped to the caller's bounds.  The iterate is clipped
+// to l / d and u / d, and (l / d) d can land one ulp outside [l, u]: the result contract promises l <= x <= u exactly
+// (include/dervet_hip.h dvh_result, tests/result_contract.py), so every tier's write-back goes through here.  A NaN
+// (a diverged window, status NUMERICAL) stays NaN: fmin / fmax alone would turn it into a bound.
+__host__ __device__ inline double unscale_x(double xs, double d, double l, double u) {
+  const double v = xs * d;
+  return v != v ? v : fmin(fmax(v, l), u);
+}
+
 // Kernel-side copy of dvh_options (POD, passed by value).
 struct Opts {
   double eps, step_safety, rho, b_suff, b_nec, b_art, theta;

@@ -804,9 +804,12 @@ __global__ __launch_bounds__(B) void pdhg_kernel(const Batch b, const Work w, co
   for (int s = 0; s < XS; ++s)
     if (ts[s] >= 0) {
       const int j = tid + s * B;
-      xo_g[j] *= dcv[j];
+      xo_g[j] = unscale_x(xo_g[j], dcv[j], b.l[W.on + j], b.u[W.on + j]);
     }
-  for (int L = tid; L < nlt; L += B) b.x[W.on + lxi[L]] = lx[5 * kLMax + L] * dcv[lxi[L]];
+  for (int L = tid; L < nlt; L += B) {
+    const int j = lxi[L];
+    b.x[W.on + j] = unscale_x(lx[5 * kLMax + L], dcv[j], b.l[W.on + j], b.u[W.on + j]);
+  }
 #pragma unroll
   for (int s = 0; s < YS; ++s)
     if (ks[s] >= 0) {
@@ -1613,8 +1616,14 @@ __global__ __launch_bounds__(B) __attribute__((amdgpu_waves_per_eu(WPE))) void p
   // outputs: the last check's T(z_k), unscaled
 #pragma unroll
   for (int s = 0; s < XS; ++s)
-    if (xown[s]) xo_g[tid + s * B] = (PL ? lds_ld(xst[s] + D) : xo_g[tid + s * B]) * dcv[tid + s * B];
-  for (int L = tid; L < nlx; L += B) xo_g[lxi[L]] = lx[5 * kLMax + L] * dcv[lxi[L]];
+    if (xown[s]) {
+      const int j = tid + s * B;
+      xo_g[j] = unscale_x(PL ? lds_ld(xst[s] + D) : xo_g[j], dcv[j], b.l[W.on + j], b.u[W.on + j]);
+    }
+  for (int L = tid; L < nlx; L += B) {
+    const int j = lxi[L];
+    xo_g[j] = unscale_x(lx[5 * kLMax + L], dcv[j], b.l[W.on + j], b.u[W.on + j]);
+  }
 #pragma unroll
   for (int s = 0; s < YS; ++s)
     if (yown[s]) yo_g[tid + s * B] = (PL ? lds_ld(yst[s] + D) : yo_g[tid + s * B]) * drv[tid + s * B];

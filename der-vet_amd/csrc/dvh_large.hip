@@ -581,7 +581,7 @@ __global__ __launch_bounds__(LB) void lg_restart(LgArgs a) {
 __global__ __launch_bounds__(LB) void lg_finish(LgArgs a) {
   const LgState* st = a.st;
   const int t = blockIdx.x * LB + threadIdx.x;
-  if (t < a.n) a.ox[t] = a.dc[t] * a.xo[t];
+  if (t < a.n) a.ox[t] = unscale_x(a.xo[t], a.dc[t], a.l[t], a.u[t]);
   if (t < a.m) a.oy[t] = a.dr[t] * a.yo[t];
   if (t == 0) {
     a.ostats[0] = st->pobj;

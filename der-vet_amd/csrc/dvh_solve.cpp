@@ -24,7 +24,10 @@ dvh::Opts make_opts(const dvh_options& p) {
   o.b_art = p.restart_artificial;
   o.theta = p.primal_weight_theta;
   o.max_iters = p.max_iters;
-  o.check_every = p.check_every;
+  // a limit below the check period shortens the period (as the grid-wide path always did, dvh_large.hip): every tier
+  // then runs a check at the limit, so an ITER_LIMIT window returns a checked candidate and its KKT numbers -- not
+  // the NaN of "no check ran" and whatever the candidate images held (include/dervet_hip.h dvh_result)
+  o.check_every = std::max(1, std::min(p.check_every, p.max_iters));
   o.kkt_every = p.kkt_every;
   o.ruiz_iters = p.ruiz_iters;
   o.power_iters = p.power_iters;

@@ -18,7 +18,13 @@ std::string validate_lp(const dvh_lp& lp, int k) {
     return buf;
   }
   const int m = lp.m_eq + lp.m_ineq;
-  if (!lp.indptr || (lp.nnz > 0 && (!lp.indices || !lp.data)) || !lp.c || (m > 0 && !lp.q) || !lp.l || !lp.u) {
+  if (m == 0) {
+    // a bound-constrained problem without a row: no tier is written for it (the grid-wide path would launch its row
+    // kernels over an empty grid, the band forms read T = m_eq - 1) and the host restatements do not take it either
+    snprintf(buf, sizeof buf, "window %d: no constraint rows (m_eq + m_ineq = 0) is not supported", k);
+    return buf;
+  }
+  if (!lp.indptr || (lp.nnz > 0 && (!lp.indices || !lp.data)) || !lp.c || !lp.q || !lp.l || !lp.u) {
     snprintf(buf, sizeof buf, "window %d: null array", k);
     return buf;
   }

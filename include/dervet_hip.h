@@ -74,8 +74,11 @@ typedef struct dvh_options {
                               /*    (unscaled, e.g. a similar window's solution); 0: x = proj(0), y = 0 */
   int32_t certify_iters;      /* iteration cap of the certificate pass (certify below); 0 = default, 65536          */
   double eps_obj;             /* objective-error termination (0 = off), default 1e-6: besides the KKT test, */
-                              /* |pobj - dobj| + ||y||_2 ||r_p||_2 <= eps_obj (1 + |pobj|) (unscaled), an    */
-                              /* estimate of |pobj - opt| (gap + the dual-weighted primal residual)          */
+                              /* |pobj - dobj| + ||y||_2 ||r_p||_2 + sum_j |r_d,j| |x_j| <= eps_obj (1 + |pobj|) */
+                              /* (unscaled), an estimate of |pobj - opt|: the gap, the dual-weighted primal   */
+                              /* residual, and what the dual residual r_d = c - K'y - lambda lets the dual    */
+                              /* objective overstate the optimum by.  The band kernel's ICE form (config-5    */
+                              /* windows) applies the test without the last term                              */
   int32_t kkt_predict;        /* 0 = off (default).  P > 0 (band and ELL kernels; the other tiers ignore it): a  */
                               /* due KKT check is skipped while its predicted outcome, the last check's worst   */
                               /* ratio max(pres, dres, gap) / eps scaled by the fixed-point residual's decrease  */
@@ -91,7 +94,8 @@ typedef struct dvh_options {
 typedef struct dvh_lp {
   int32_t n;                  /* variables                          */
   int32_t m_eq;               /* equality rows (first)              */
-  int32_t m_ineq;             /* >= rows (after the equalities)     */
+  int32_t m_ineq;             /* >= rows (after the equalities); m_eq + m_ineq >= 1 (a window without a row is   */
+                              /* rejected with a message); rows and columns without an entry are allowed        */
   int32_t nnz;
   const int32_t* indptr;      /* [m_eq + m_ineq + 1] CSR row pointers (0-based)                  */
   const int32_t* indices;     /* [nnz] column indices                                           */
@@ -105,6 +109,19 @@ typedef struct dvh_lp {
   int32_t reserved;
 } dvh_lp;
 
+/* x, y: the candidate T(z_k) of the window's last termination check, unscaled; obj and the three relative KKT numbers
+ * are that check's, computed from the same x, y (lambda: the part of c - K'y the finite bounds carry: all of it on a
+ * boxed column, its positive part with a lower bound only, its negative part with an upper bound only, none on a free
+ * column; pobj = c'x + c0; dobj = q'y + sum_j l_j max(lambda_j, 0) + sum_j u_j min(lambda_j, 0) + c0; >= rows count
+ * max(q - Kx, 0)).  DVH_OPTIMAL: the three numbers are <= eps and the eps_obj test holds (dvh_options).
+ * DVH_ITER_LIMIT: a termination check always runs at the limit -- the check period is min(check_every, max_iters) on
+ * every tier and in both host restatements (oracle/) -- so x, y and the numbers are those of a checked candidate at or
+ * before max_iters, never unset.  x is clipped to [l, u] on the way out (the unscaling can round past a bound).
+ * The numbers are NaN only where no iteration ran: a window reported DVH_NUMERICAL by the set-up (more than 64 rows or
+ * columns of more than 32 entries), with x, y untouched; a crossed-bounds window (PRIMAL_INFEASIBLE, 0 iterations)
+ * has obj NaN and the others 0.  A window that ends DVH_NUMERICAL while iterating (a non-finite objective) returns the
+ * diverged candidate: its x, y may hold NaN or infinities and mean nothing.  tests/kkt_ref.py recomputes all of it on
+ * the host (tests/test_gpu_result_contract.py, tests/test_gpu_planted.py). */
 typedef struct dvh_result {
   double* x;                  /* caller-allocated [n] or NULL                                   */
   double* y;                  /* caller-allocated [m] or NULL (duals; >= rows have y >= 0)       */

@@ -73,7 +73,10 @@ struct Out {
   int status = DVH_ITER_LIMIT, iters = 0;
 };
 
-void solve_one(const dvh_lp& lp, const dvh_options& o, const double* x0, const double* y0, Out& out) {
+void solve_one(const dvh_lp& lp, const dvh_options& opts, const double* x0, const double* y0, Out& out) {
+  // a limit below the check period shortens the period (csrc/dvh_solve.cpp make_opts): a check runs at the limit
+  dvh_options o = opts;
+  o.check_every = std::max(1, std::min(opts.check_every, opts.max_iters));
   const int n = lp.n, m = lp.m_eq + lp.m_ineq, me = lp.m_eq;
   out.x.assign(n, 0.0);
   out.y.assign(m, 0.0);

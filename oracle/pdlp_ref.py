@@ -71,6 +71,8 @@ def solve(lp, opts=None, trace=None):
     import scipy.sparse as sp
     o = dict(DEFAULTS)
     o.update(opts or {})
+    # a limit below the check period shortens the period (csrc/dvh_solve.cpp make_opts): a check runs at the limit
+    o["check_every"] = max(1, min(o["check_every"], o["max_iters"]))
     K = sp.csr_matrix(lp["K"])
     m, n = K.shape
     m_eq = int(lp["m_eq"])

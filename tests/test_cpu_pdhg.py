@@ -71,3 +71,18 @@ def test_crossed_bounds_report_primal_infeasible_without_iterating():
     res = CpuPdhgSolver(threads=2).solve(lps)
     assert res[1].status_name == "infeasible" and res[1].iters == 0
     assert res[0].status == 0 and res[2].status == 0
+
+
+def test_a_window_without_rows_is_rejected_with_a_message():
+    """m_eq + m_ineq = 0 passes no tier (csrc/dvh_validate.cpp): the shared validation refuses it, as the GPU library
+    does (tests/test_gpu_result_contract.py)."""
+    import numpy as np
+    from dervet_hip.solver import WindowLP
+    lp = WindowLP(np.zeros(1, np.int32), np.zeros(0, np.int32), np.zeros(0), np.array([1.0]), np.zeros(0), np.zeros(1),
+                  np.ones(1), 0, 0.0)
+    s = CpuPdhgSolver(threads=1)
+    with pytest.raises(RuntimeError):
+        s.solve([lp])
+    assert "no constraint rows" in s._lib.dvh_last_error(s._h).decode()
+    ok = [w for g in scenarios.config4([0]) for w in builder.group_window_lps(g)][:1]
+    assert s.solve(ok)[0].status == 0
