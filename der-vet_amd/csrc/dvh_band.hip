@@ -92,6 +92,11 @@ struct BandTune {
   // and config 2 15.0-15.2k -> 16.8-16.9k windows/s; the ICE form spills 66 VGPRs instead of 19 with it and ran
   // config 5 at 131.0k against 131.2k windows/s (profiles/band_loop_variants.log)
   static constexpr bool plain_loop = !ICE;
+  // wave 0's dual half-step: its LDS reads -- the next lane's ene, the tau x-bar and, for the init row, ene_0 -- in
+  // front of the s_setprio 0 behind the first barrier, and the init row's lane-masked block without a read and a wait
+  // of its own (see the dual half-step).  Bench -3.5 % per step; the early ene_0 alone -2 %, the reads in front of
+  // s_setprio alone within the spread (profiles/band_w0_bench_ab.log).  The other forms keep their machine code.
+  static constexpr bool w0_reads_first = !ICE && S == 3;
 };
 // Wave 0, whose primal half-step carries the tau column's reduction and update -- the iteration's critical path, on
 // which the other waves wait at the first barrier -- runs that half-step at this s_setprio level, so that the SIMD it
@@ -169,9 +174,10 @@ __device__ __forceinline__ RowKkt row_kkt_fn(double kv, double qi, double yi, fl
 // and the primal weight), and the write-back recomputes w = u / d - l / d with the set-up's operations (bit-identical).
 constexpr int kNeedsPlain = -3;
 // DVH_BAND_PROBE (A/B builds only, scripts/probe_band_latency.py): every wave accumulates the shader-clock cycles of
-// its iterations' four segments -- primal half-step, wait at the first barrier, dual half-step, wait at the second --
-// and of the checks, and lane 0 writes them over x[6 wid .. 6 wid + 4] of its window at the end, with the wave's
-// HW_ID register (SIMD, CU, SE, workgroup slot) in x[6 wid + 5].
+// its iterations' five segments -- primal half-step, wait at the first barrier, dual half-step up to the init row, the
+// init row's block (lane kInitLane of wave 0; next to nothing on the other waves), wait at the second barrier -- and of
+// the checks, and lane 0 writes them over x[7 wid .. 7 wid + 5] of its window at the end, with the wave's HW_ID register
+// (SIMD, CU, SE, workgroup slot) in x[7 wid + 6].
 #ifndef DVH_BAND_PROBE
 #define DVH_BAND_PROBE 0
 #endif
@@ -1037,7 +1043,8 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
   };
   // (DVH_BAND_PROBE) stamps label the segment they end; a segment is added at the NEXT stamp, so that no stamp waits
   // for its own s_memtime (a stamp's value is first used after the barrier that follows it)
-  unsigned pacc[5] = {0u, 0u, 0u, 0u, 0u};
+  constexpr int kProbeSegs = 6;
+  unsigned pacc[kProbeSegs] = {0u, 0u, 0u, 0u, 0u, 0u};
   unsigned long long pt1 = 0ull, pt2 = 0ull;
   auto pstamp = [&](int seg) __attribute__((always_inline)) {
     if constexpr (DVH_BAND_PROBE) {
@@ -1045,7 +1052,7 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
       if (seg < 0) {
         pt1 = pt2 = t;
       } else {
-        pacc[(seg + 4) % 5] += (unsigned)(pt1 - pt2);
+        pacc[(seg + kProbeSegs - 1) % kProbeSegs] += (unsigned)(pt1 - pt2);
         pt2 = pt1;
         pt1 = t;
       }
@@ -1055,7 +1062,7 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
     constexpr bool CHECK = decltype(chk_tag)::value;
     constexpr bool W0 = decltype(w0_tag)::value;
     if constexpr (W0) __builtin_amdgcn_s_setprio(kTauWavePrio);  // until the first barrier
-    pstamp(4);  // (the check code since the last iteration, or the loop entry)
+    pstamp(5);  // (the check code since the last iteration, or the loop entry)
     if (kin - kbase >= kWave) {
       kbase = kin;
       hw = hload(kin);
@@ -1144,14 +1151,11 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
         for (int r = 0; r < NR; ++r) asm volatile("" ::"v"(kx[s][r]));
     }
     lds_barrier();
-    if constexpr (W0) __builtin_amdgcn_s_setprio(0);
-    pstamp(1);
-    // ---------------- dual half-step
-    {
-      // every LDS read of the half-step first (the next lane's ene, the tau columns' x-bar), before any LDS store:
-      // issued together, one wait instead of one per read
-      const double xen = XE[tid + 1];
-      double xtv[S];
+    // every LDS read of the dual half-step together (the next lane's ene, the tau columns' x-bar), before any LDS
+    // store: one wait instead of one per read
+    double xen, xtv[S], xe0 = 0.0;
+    auto dual_reads = [&]() __attribute__((always_inline)) {
+      xen = XE[tid + 1];
       if constexpr (J1) {  // one tau column: one read
         const double xt0 = XT[0];
 #pragma unroll
@@ -1160,6 +1164,21 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
 #pragma unroll
         for (int s = 0; s < S; ++s) xtv[s] = lds_ld(xta[s]);
       }
+    };
+    // (Tune::w0_reads_first) wave 0 issues them in front of the priority drop, and the init row's ene_0 (lane kInitLane;
+    // a broadcast read) with them: s_setprio is a scheduling boundary, so the reads behind it started after the x-bar and
+    // K x-bar work the compiler sinks across the barrier and were waited for at once; in front of it that work runs under
+    // their latency, and the init row's block at the end of the half-step has nothing left to wait for
+    constexpr bool RF = W0 && Tune::w0_reads_first;
+    if constexpr (RF) {
+      dual_reads();
+      xe0 = XE[0];
+    }
+    if constexpr (W0) __builtin_amdgcn_s_setprio(0);
+    pstamp(1);
+    // ---------------- dual half-step
+    {
+      if constexpr (!RF) dual_reads();
       kfin_next(S - 1, kx[S - 1], xen);
       // the >= rows first: their duals feed the tau partials, whose wave reduction then has the SOE rows' work
       // beside it
@@ -1173,10 +1192,11 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
 #pragma unroll
       for (int s = !W0 ? S - 1 : 0; s < S; ++s) row_step(s, 0);  // (the lane-local SOE rows: see below)
       YS[tid + 1] = y[S - 1][0];
+      pstamp(2);
       if (W0 || (!J1 && wid == 0)) {  // init row (lane kInitLane): ene_0 = target; (J1: wave 0 is always W0)
         if (ilane) {
           const double y0 = sp[0], ya0 = sp[1];
-          const double q1 = fma(sigma, sp[3] - sp[4] * XE[0], y0);
+          const double q1 = fma(sigma, sp[3] - sp[4] * (RF ? xe0 : XE[0]), y0);
           if (CHECK) {
             const double d = y0 - q1, da = q1 - ya0;
             mv2 += d * d;
@@ -1191,7 +1211,7 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
     }
     ++it;
     ++kin;
-    pstamp(2);
+    pstamp(3);
     // Wave 0 finishes this iteration's Halpern blends (x = ca x-bar + cb x-anchor, and the rows') before the second
     // barrier, where it waits for the others anyway: the compiler sank them past the barrier, to the head of wave 0's
     // next primal half-step -- in front of the tau reduction (profiles/r06j_pin_blend.log).
@@ -1219,7 +1239,7 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
 #pragma unroll
         for (int r = 2; r < NR; ++r) row_step(s, r);
     }
-    pstamp(3);
+    pstamp(4);
   };
 
   using F = std::integral_constant<bool, false>;
@@ -1244,6 +1264,8 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
   // out of the other waves' body -- the J > 1 tau update, the init row, the per-step XT reads -- are lane-masked blocks
   // and LDS reads without a barrier: both bodies still pass both barriers once per trip, and the other waves' body
   // becomes an innermost loop without the two child loops over the tau columns (profiles/band_j1_shape.txt).
+  // Tune::w0_reads_first moves LDS reads of wave 0's body to the other side of an s_setprio and adds one broadcast read:
+  // no barrier, no branch and no lane mask is added or moved (profiles/band_w0_shape.txt).
   while (it < o.max_iters) {
     if constexpr (Tune::plain_loop) {
       if (ck > 1) {  // the ck - 1 plain iterations up to the next check, or those left to max_iters
@@ -1509,14 +1531,14 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
   if (tlane) xo_g[3 * T + lane] = unscale_x(sp[5], dcf(3 * T + lane), lraw[3 * T + lane], uraw[3 * T + lane]);
   if (ilane) yo_g[0] = sp[2] * drf(0);
   if constexpr (DVH_BAND_PROBE) {
-    pstamp(4);
-    pacc[4] += (unsigned)(pt1 - pt2);
+    pstamp(kProbeSegs - 1);
+    pacc[kProbeSegs - 1] += (unsigned)(pt1 - pt2);
     unsigned hw = 0;
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
     __syncthreads();
     if (lane == 0) {
-      for (int u = 0; u < 5; ++u) xo_g[6 * wid + u] = (double)pacc[u];
-      xo_g[6 * wid + 5] = (double)hw;
+      for (int u = 0; u < kProbeSegs; ++u) xo_g[(kProbeSegs + 1) * wid + u] = (double)pacc[u];
+      xo_g[(kProbeSegs + 1) * wid + kProbeSegs] = (double)hw;
     }
   }
   if (tid == 0) {
