@@ -97,10 +97,65 @@ struct BandTune {
   // of its own (see the dual half-step).  Bench -3.5 % per step; the early ene_0 alone -2 %, the reads in front of
   // s_setprio alone within the spread (profiles/band_w0_bench_ab.log).  The other forms keep their machine code.
   static constexpr bool w0_reads_first = !ICE && S == 3;
+  // wave 0's plain iteration: the SOE rows of the lane's steps 0 .. S - 2 behind the second barrier, as on the other
+  // waves, and no blend pinned in front of that barrier.  Wave 0 is the last wave there and waits 375 cycles at the
+  // first (profiles/band_reads_latency.log), so the 33 FP64 instructions leave the span where it is critical.  Alone:
+  // bench 343.1-345.3 against the parent's 345.4-346.0 ms per step, inside the spread; it is kept for what it gives
+  // together with reads_ahead (profiles/band_reads_bench_ab.log).  Check iterations keep the parent's order, in which
+  // their movement sums are accumulated.
+  static constexpr bool w0_late = !ICE && S == 3;
+  // every wave's plain iteration: the LDS reads of the next primal half-step (YS[tid], the nine costs, wave 0's four tau
+  // partials) issue directly behind the second barrier and are carried across the loop's back edge in registers; the
+  // x blends and the late rows run under their latency, and the reads' first use follows that block (see the end of
+  // iterate).  With w0_late: bench 337.9-338.5 against the parent's 344.7-345.7 ms per step, 17 spilled VGPRs as before
+  // (profiles/band_reads_bench_ab.log, band_reads_shape.txt).
+  static constexpr bool reads_ahead = !ICE && S == 3;
 };
-// Wave 0, whose primal half-step carries the tau column's reduction and update -- the iteration's critical path, on
-// which the other waves wait at the first barrier -- runs that half-step at this s_setprio level, so that the SIMD it
-// shares with the other window's wave issues its instructions first (profiles/r06a_ab.log).
+// (BandTune::reads_ahead) What a plain iteration's primal half-step reads from LDS -- YS[tid], the lane's nine costs, on
+// wave 0 the four tau partials -- is read behind the second barrier of the iteration before it (in front of the loop for
+// its first trip; the last trip's reads are not used: the check iteration reads for itself) and carried across the back
+// edge in this object's registers.  YS and TP are written in front of the second barrier and next behind the first, the
+// costs at the set-up only, so the values are the ones the iteration's own reads would return.  hold(), at the
+// iteration's end, keeps the compiler from sinking the reads back to their users at the loop's head; the wait it implies
+// has the blend block in front of it.  The live range is that block: 10 VGPR pairs, 14 on wave 0.
+template <int B, int S>
+struct BandAhead {
+  static constexpr int NW = B / kWave;
+  const double *tp, *ys, *cq;  // TP + lane, YS + tid, CQ + tid (LDS)
+  double y, c[S][3], t[NW];
+  double xb[S][3];  // x-bar of the battery columns, for the blends behind the second barrier
+  template <bool W0>
+  __device__ __forceinline__ void read() {
+    if constexpr (W0) {
+#pragma unroll
+      for (int r = 0; r < NW; ++r) t[r] = tp[r * kWave];
+    }
+    y = *ys;
+#pragma unroll
+    for (int s = 0; s < S; ++s)
+#pragma unroll
+      for (int v = 0; v < 3; ++v) c[s][v] = cq[(v * S + s) * B];
+  }
+  template <bool W0>
+  __device__ __forceinline__ void hold() {
+    if constexpr (W0) {
+#pragma unroll
+      for (int r = 0; r < NW; ++r) t[r] = opaque(t[r]);
+    }
+    y = opaque(y);
+#pragma unroll
+    for (int s = 0; s < S; ++s)
+#pragma unroll
+      for (int v = 0; v < 3; ++v) c[s][v] = opaque(c[s][v]);
+  }
+};
+struct BandNoAhead {};
+// Wave 0, whose primal half-step carries the tau column's reduction and update, runs that half-step at this s_setprio
+// level, so that the SIMD it shares with the other window's wave issues its instructions first (profiles/r06a_ab.log).
+// Wave 0 is no longer the wave the others wait for at the first barrier -- it waits there itself, for waves 1-3
+// (profiles/band_reads_latency.log) -- but the raise still pays: on top of w0_late and reads_ahead, no raised priority
+// ran the bench at 350.2-350.7 ms per step, level 1 at 337.9-338.1, the raise ended at the tau reduction's last DPP
+// level at 346.7-348.2, against 337.3-339.2 for this (profiles/band_reads_bench_ab.log).
 constexpr int kTauWavePrio = 2;
 
 // KKT pieces of one column / one row.  Scale-free where the check compares large terms: the objectives' sums c'x, q'y
@@ -174,10 +229,12 @@ __device__ __forceinline__ RowKkt row_kkt_fn(double kv, double qi, double yi, fl
 // and the primal weight), and the write-back recomputes w = u / d - l / d with the set-up's operations (bit-identical).
 constexpr int kNeedsPlain = -3;
 // DVH_BAND_PROBE (A/B builds only, scripts/probe_band_latency.py): every wave accumulates the shader-clock cycles of
-// its iterations' five segments -- primal half-step, wait at the first barrier, dual half-step up to the init row, the
-// init row's block (lane kInitLane of wave 0; next to nothing on the other waves), wait at the second barrier -- and of
-// the checks, and lane 0 writes them over x[7 wid .. 7 wid + 5] of its window at the end, with the wave's HW_ID register
-// (SIMD, CU, SE, workgroup slot) in x[7 wid + 6].
+// its iterations' seven segments -- primal half-step, wait at the first barrier, dual half-step up to the init row, the
+// init row's block (lane kInitLane of wave 0; next to nothing on the other waves), what is left in front of the second
+// barrier (the blends, where they are placed there), the wait at the second barrier, what follows it up to the
+// iteration's end (late rows, blends placed there) -- and of the checks, and lane 0 writes them over
+// x[9 wid .. 9 wid + 7] of its window at the end, with the wave's HW_ID register (SIMD, CU, SE, workgroup slot) in
+// x[9 wid + 8].
 #ifndef DVH_BAND_PROBE
 #define DVH_BAND_PROBE 0
 #endif
@@ -753,10 +810,11 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
   // The iteration's forms with the objective / right-hand side folded into the FMA chains: K^T y - c for the
   // primal half-step (x + tau (K^T y - c) = x - tau (c - K^T y)) and K x - q for the dual one (y - sigma (K x - q)):
   // one FP64 operation fewer per column and per row than forming the difference afterwards.
-  auto ktr_c = [&](int s, const double (&vr)[NR], double vprev, double (&out)[NC]) {
-    out[0] = fma(kd[s][0], vr[1], fma(ks[s][0], vr[0], -cof(s, 0)));
-    out[1] = fma(kd[s][1], vr[1], fma(ks[s][1], vr[0], -cof(s, 1)));
-    out[2] = fma(ks[s][2], vr[0], fma(kpv(s), vprev, -cof(s, 2)));
+  // (cs: the step's three battery costs in registers -- BandTune::reads_ahead; a constant after inlining)
+  auto ktr_c = [&](int s, const double (&vr)[NR], double vprev, double (&out)[NC], const double* cs = nullptr) {
+    out[0] = fma(kd[s][0], vr[1], fma(ks[s][0], vr[0], -(cs ? cs[0] : cof(s, 0))));
+    out[1] = fma(kd[s][1], vr[1], fma(ks[s][1], vr[0], -(cs ? cs[1] : cof(s, 1))));
+    out[2] = fma(ks[s][2], vr[0], fma(kpv(s), vprev, -(cs ? cs[2] : cof(s, 2))));
     if constexpr (ICE) {
       out[3] = fma(kb[s][0], vr[3], fma(ka[s][0], vr[2], fma(kd[s][3], vr[1], -cof(s, 3))));
       out[4] = fma(kb[s][1], vr[3], fma(ka[s][1], vr[2], -cof(s, 4)));
@@ -1043,8 +1101,8 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
   };
   // (DVH_BAND_PROBE) stamps label the segment they end; a segment is added at the NEXT stamp, so that no stamp waits
   // for its own s_memtime (a stamp's value is first used after the barrier that follows it)
-  constexpr int kProbeSegs = 6;
-  unsigned pacc[kProbeSegs] = {0u, 0u, 0u, 0u, 0u, 0u};
+  constexpr int kProbeSegs = 8;
+  unsigned pacc[kProbeSegs] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
   unsigned long long pt1 = 0ull, pt2 = 0ull;
   auto pstamp = [&](int seg) __attribute__((always_inline)) {
     if constexpr (DVH_BAND_PROBE) {
@@ -1058,11 +1116,24 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
       }
     }
   };
-  auto iterate = [&](auto chk_tag, auto w0_tag) __attribute__((always_inline)) {
+  // (Tune::reads_ahead) the reads carried from one plain iteration to the next (BandAhead).  iterate takes the object as
+  // an argument and keeps no local of its own for this: one more capture of that lambda, a local array in it or a
+  // generic ktr_c each changed the register allocation of the forms that do not use any of it.
+  using F = std::integral_constant<bool, false>;
+  using Tt = std::integral_constant<bool, true>;
+  std::conditional_t<Tune::reads_ahead, BandAhead<B, S>, BandNoAhead> ah;
+  if constexpr (Tune::reads_ahead) {
+    ah.tp = TP + lane;
+    ah.ys = YS + tid;
+    ah.cq = CQ + tid;
+  }
+  auto iterate = [&](auto chk_tag, auto w0_tag, auto& ahd) __attribute__((always_inline)) {
     constexpr bool CHECK = decltype(chk_tag)::value;
     constexpr bool W0 = decltype(w0_tag)::value;
+    constexpr bool RA = !CHECK && Tune::reads_ahead;
+    constexpr bool LATE = !W0 || (!CHECK && Tune::w0_late);
     if constexpr (W0) __builtin_amdgcn_s_setprio(kTauWavePrio);  // until the first barrier
-    pstamp(5);  // (the check code since the last iteration, or the loop entry)
+    pstamp(7);  // (the check code since the last iteration, or the loop entry)
     if (kin - kbase >= kWave) {
       kbase = kin;
       hw = hload(kin);
@@ -1090,7 +1161,15 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
     };
     {
       double ta0 = 0.0, ta1 = 0.0;
-      if constexpr (W0) {  // (0 + a == a: the first partials start the two chains)
+      if constexpr (W0 && RA) {  // (the partials read behind the last second barrier, summed in the same order)
+        ta0 = ahd.t[0];
+        if (NW > 1) ta1 = ahd.t[1];
+#pragma unroll
+        for (int r = 2; r < NW; r += 2) {
+          ta0 += ahd.t[r];
+          if (r + 1 < NW) ta1 += ahd.t[r + 1];
+        }
+      } else if constexpr (W0) {  // (0 + a == a: the first partials start the two chains)
         ta0 = TP[lane];
         if (NW > 1) ta1 = TP[kWave + lane];
 #pragma unroll
@@ -1100,9 +1179,14 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
         }
       }
       double kty[S][NC], xb[S][NC];
-      const double ysp = YS[tid];
+      if constexpr (RA) {
 #pragma unroll
-      for (int s = 0; s < S; ++s) ktr_c(s, y[s], s == 0 ? ysp : y[s > 0 ? s - 1 : 0][0], kty[s]);
+        for (int s = 0; s < S; ++s) ktr_c(s, y[s], s == 0 ? ahd.y : y[s > 0 ? s - 1 : 0][0], kty[s], ahd.c[s]);
+      } else {
+        const double ysp = YS[tid];
+#pragma unroll
+        for (int s = 0; s < S; ++s) ktr_c(s, y[s], s == 0 ? ysp : y[s > 0 ? s - 1 : 0][0], kty[s]);
+      }
 #pragma unroll
       for (int s = 0; s < S; ++s) {
 #pragma unroll
@@ -1128,7 +1212,10 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
             }
             xpi(v, s) = p1;
           }
-          x[s][v] = fma(ca, xb[s][v], cb * xa[s][v]);
+          if constexpr (RA)
+            ahd.xb[s][v] = xb[s][v];
+          else
+            x[s][v] = fma(ca, xb[s][v], cb * xa[s][v]);
         }
       }
       XE[tid] = xb[0][2];
@@ -1190,7 +1277,7 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
       }
       if (J > 0) tau_parts_of(y);
 #pragma unroll
-      for (int s = !W0 ? S - 1 : 0; s < S; ++s) row_step(s, 0);  // (the lane-local SOE rows: see below)
+      for (int s = LATE ? S - 1 : 0; s < S; ++s) row_step(s, 0);  // (the lane-local SOE rows: see below)
       YS[tid + 1] = y[S - 1][0];
       pstamp(2);
       if (W0 || (!J1 && wid == 0)) {  // init row (lane kInitLane): ene_0 = target; (J1: wave 0 is always W0)
@@ -1212,10 +1299,11 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
     ++it;
     ++kin;
     pstamp(3);
-    // Wave 0 finishes this iteration's Halpern blends (x = ca x-bar + cb x-anchor, and the rows') before the second
-    // barrier, where it waits for the others anyway: the compiler sank them past the barrier, to the head of wave 0's
-    // next primal half-step -- in front of the tau reduction (profiles/r06j_pin_blend.log).
-    if constexpr (W0) {
+    // Wave 0's check iteration finishes its Halpern blends (x = ca x-bar + cb x-anchor, and the rows') before the second
+    // barrier.  The plain iteration did so too (profiles/r06j_pin_blend.log, when wave 0 waited for the others at that
+    // barrier); since Tune::w0_reads_first it is the wave the others wait for there, and with Tune::w0_late its plain
+    // iteration leaves the blends to the far side of the barrier, as the other waves do.
+    if constexpr (W0 && !LATE) {
 #pragma unroll
       for (int s = 0; s < S; ++s) {
 #pragma unroll
@@ -1224,12 +1312,27 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
         for (int r = 0; r < NR; ++r) asm volatile("" ::"v"(y[s][r]));
       }
     }
+    pstamp(4);
     lds_barrier();
+    pstamp(5);  // (directly behind the barrier: the wait alone, without the late rows)
     // The waves without the tau column update the SOE rows of their lanes' steps 0 .. S - 2, and the two ICE rows, after
     // the barrier instead of before it (those duals are read only by the lane's own next primal half-step), so that they
     // reach the barrier -- which wave 0's next tau reduction waits behind -- sooner (profiles/r06s_ab.log,
-    // r06m_late_ice.log).
-    if constexpr (!W0) {
+    // r06m_late_ice.log).  With Tune::w0_late wave 0's plain iteration does the same: it is the wave the others wait for at
+    // this barrier.
+    // (Tune::reads_ahead) the next primal half-step's reads first, then -- nothing crosses the sched_barrier, without it
+    // the scheduler issued the reads behind the blends and waited for them at once -- the x blends, placed here in the
+    // source, and the late rows under the reads' latency; hold_ahead ends the block.  No barrier, branch or lane mask
+    // is involved: reads, lane-local arithmetic and two scheduling directives.
+    if constexpr (RA) {
+      ahd.template read<W0>();
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int s = 0; s < S; ++s)
+#pragma unroll
+        for (int v = 0; v < NC; ++v) x[s][v] = fma(ca, ahd.xb[s][v], cb * xa[s][v]);
+    }
+    if constexpr (LATE) {
 #pragma unroll
       for (int s = 0; s < S - 1; ++s) row_step(s, 0);
     }
@@ -1239,11 +1342,10 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
 #pragma unroll
         for (int r = 2; r < NR; ++r) row_step(s, r);
     }
-    pstamp(4);
+    if constexpr (RA) ahd.template hold<W0>();
+    pstamp(6);
   };
 
-  using F = std::integral_constant<bool, false>;
-  using Tt = std::integral_constant<bool, true>;
   pstamp(-1);
   // The plain iterations between two checks run in an innermost loop of their own, one per wave kind
   // (Tune::plain_loop).  As `if (--ck != 0) { iterate; continue; }` in this loop, the plain iteration was a branch of
@@ -1266,32 +1368,42 @@ __device__ __forceinline__ void band_window(const Batch& b, const Work& w, const
   // becomes an innermost loop without the two child loops over the tau columns (profiles/band_j1_shape.txt).
   // Tune::w0_reads_first moves LDS reads of wave 0's body to the other side of an s_setprio and adds one broadcast read:
   // no barrier, no branch and no lane mask is added or moved (profiles/band_w0_shape.txt).
+  // Tune::w0_late and Tune::reads_ahead keep all of this as well.  The first moves lane-local row updates and blends of
+  // wave 0's body from one side of the second barrier to the other.  The second adds LDS reads in front of each loop
+  // (straight-line, every lane, no barrier) and moves the body's reads of YS, TP and the costs from its head to its
+  // tail, behind the second barrier of the same trip: between that barrier and the next trip's first barrier nothing
+  // writes YS or TP, so the carried values are what the head would have read, on every trip including the first; the
+  // trip that leaves the loop reads once for nothing.  np, the exit branch and both barriers are untouched, so both
+  // bodies still pass both barriers once per trip on every path (profiles/band_reads_shape.txt), and the two traps
+  // named above apply unchanged: nothing here depends on the lane.
   while (it < o.max_iters) {
     if constexpr (Tune::plain_loop) {
       if (ck > 1) {  // the ck - 1 plain iterations up to the next check, or those left to max_iters
         int np = min(ck - 1, o.max_iters - it);
         ck -= np;
         if (w0) {
-          do iterate(F(), Tt());
+          if constexpr (Tune::reads_ahead) ah.template read<true>();
+          do iterate(F(), Tt(), ah);
           while (--np != 0);
         } else {
-          do iterate(F(), F());
+          if constexpr (Tune::reads_ahead) ah.template read<false>();
+          do iterate(F(), F(), ah);
           while (--np != 0);
         }
         continue;
       }
     } else if (--ck != 0) {
       if (w0)
-        iterate(F(), Tt());
+        iterate(F(), Tt(), ah);
       else
-        iterate(F(), F());
+        iterate(F(), F(), ah);
       continue;
     }
     ck = chk;
     if (w0)
-      iterate(Tt(), Tt());
+      iterate(Tt(), Tt(), ah);
     else
-      iterate(Tt(), F());
+      iterate(Tt(), F(), ah);
     // ---------------- check: fixed-point residual of z_k, restart test; every kkt_every-th check the relative
     // KKT error of T(z_k) in the unscaled space (as pdhg_ell_kernel)
     const bool last = it + chk > o.max_iters;
