@@ -22,6 +22,7 @@ import functools
 
 import numpy as np
 
+import band_cases
 import planted_lp
 
 # name -> (n, m_eq, m_ineq, wy, wx, seed, options, path, copies, tier, variant, distance check)
@@ -145,27 +146,13 @@ ICE_PLANT = dict(interior_frac=0.1, active_frac=0.1)  # (at 0.4 the host referen
 
 
 def battery_window(T, J, seed=5, span=False):
-    """test_gpu_band_loop's battery + DCM window; span: the one demand period covers the middle half of the window (both
+    """band_cases' battery + DCM window; span: the one demand period covers the middle half of the window (both
     segments of a two-segment chain window)."""
-    from dervet_hip.lp import builder
-    rng = np.random.default_rng(seed)
-    load = 400 + 200 * rng.random((1, T))
-    bat = dict(E=rng.uniform(500, 2000, 1), Pch=rng.uniform(100, 400, 1), Pdis=rng.uniform(100, 400, 1),
-               rte=rng.uniform(0.8, 0.95, 1), sdr=rng.uniform(0, 1, 1), soc_target=rng.uniform(0.3, 0.9, 1),
-               ulsoc=0.95, llsoc=0.05, fixedOM=10.0, OMexpenses=rng.uniform(0, 5, 1))
-    price = rng.uniform(0.03, 0.2, (1, T))
-    if J == 0:
-        g = builder.battery_group(T, 1.0, load, bat, retail_price=price)
-    else:
-        masks = np.zeros((J, T), bool)
-        if J == 1:
-            masks[0, (T // 4 if span else 0): (3 * T // 4 if span else (T + 1) // 2)] = True
-        else:
-            for j in range(J):
-                masks[j, j::J] = True
-        g = builder.battery_group(T, 1.0, load, bat, retail_price=price, demand_masks=masks,
-                                  demand_prices=rng.uniform(5, 20, (1, J)))
-    return builder.group_window_lps(g)[0]
+    masks = None
+    if span and J == 1:
+        masks = np.zeros((1, T), bool)
+        masks[0, T // 4: 3 * T // 4] = True
+    return band_cases.window(T, J, seed, masks=masks)[0]
 
 
 @functools.lru_cache(maxsize=None)

@@ -7,10 +7,10 @@ import dataclasses
 
 import numpy as np
 import pytest
-import scipy.sparse as sp
 
 from dervet_hip.lp import builder, scenarios
 from oracle import window_lp
+from planted_lp import from_window
 
 pytestmark = pytest.mark.gpu
 
@@ -26,8 +26,7 @@ def _badly_scaled(lp):
 
 
 def _highs(lp):
-    o = dict(K=sp.csr_matrix((lp.data, lp.indices, lp.indptr), shape=(lp.m, lp.n)), q=lp.q, c=lp.c, c0=lp.c0,
-             l=lp.l, u=lp.u, m_eq=lp.m_eq)
+    o = from_window(lp)
     return o, window_lp.solve_highs(o)
 
 

@@ -7,11 +7,12 @@ grid-wide large-LP path (der-vet_amd/csrc/dvh_large.hip).
 """
 import numpy as np
 import pytest
-import scipy.sparse as sp
 
+import band_cases as bc
 from dervet_hip import BatchSolver, SolverError, WindowLP, pack
 from dervet_hip.lp import builder, scenarios
 from oracle import window_lp
+from planted_lp import from_window
 
 pytestmark = pytest.mark.gpu
 
@@ -19,15 +20,10 @@ OBJ_TOL = 1e-5
 PRES_TOL = 1e-6
 
 
-def _oracle_lp(lp):
-    K = sp.csr_matrix((lp.data, lp.indices, lp.indptr), shape=(lp.m, lp.n))
-    return dict(K=K, q=lp.q, c=lp.c, c0=lp.c0, l=lp.l, u=lp.u, m_eq=lp.m_eq)
-
-
 def _check(lps, res, what):
     worst = 0.0
     for k, (lp, r) in enumerate(zip(lps, res)):
-        olp = _oracle_lp(lp)
+        olp = from_window(lp)
         h = window_lp.solve_highs(olp)
         assert h["status"] == 0
         assert r.status == 0, f"{what} window {k}: {r.status_name} after {r.iters} iterations"
@@ -72,7 +68,7 @@ def test_config5_band_ice_path(gpu_solver):
     res = gpu_solver.solve(lps)
     _check(lps, res, "config5")
     st = gpu_solver.kernel_stats()
-    assert st["band_windows"] == 2 and st["variant"] == 9000112, st
+    assert st["band_windows"] == 2 and st["variant"] == bc.ICE, st
 
 
 def test_config5_band_ice_and_generic_kernels_agree():
@@ -138,7 +134,7 @@ def test_band_kernel_forms_agree(T):
     lps = _lps(groups)
     out = {}
     with BatchSolver(0) as s:
-        for path, variant in (("band3", 9002004), ("band1", 9000012)):
+        for path, variant in (("band3", bc.GENERIC), ("band1", bc.ONE_STEP)):
             s.set_kernel_path(path)
             out[path] = s.solve(lps)
             st = s.kernel_stats()
@@ -158,11 +154,11 @@ def test_band_kernel_form_follows_batch_size():
     big = pack(_lps(scenarios.config4(range(30)))).to_torch("cuda:0").alloc_outputs()  # 360 windows > 256 CUs
     with BatchSolver(0) as s:
         _check(small, s.solve(small), "config1 one-step")
-        assert s.kernel_stats()["variant"] == 9000012, s.kernel_stats()
+        assert s.kernel_stats()["variant"] == bc.ONE_STEP, s.kernel_stats()
         s.solve_packed(big)
         torch.cuda.synchronize()
         st = s.kernel_stats()
-        assert st["variant"] == 9002004 and st["band_windows"] == 360, st
+        assert st["variant"] == bc.GENERIC and st["band_windows"] == 360, st
         assert (big.istats.cpu().numpy()[:, 0] == 0).all()
 
 

@@ -11,11 +11,11 @@ import functools
 
 import numpy as np
 import pytest
-import scipy.sparse as sp
 
 from dervet_hip.lp import builder, scenarios
 from dervet_hip.solver import WindowLP
 from oracle import cases, window_lp
+from planted_lp import from_window
 
 pytestmark = pytest.mark.gpu
 
@@ -49,17 +49,12 @@ def _lps(T, J, variant, **kw):
     return builder.group_window_lps(_group(T, J, variant, **kw))
 
 
-def _oracle(lp):
-    return dict(K=sp.csr_matrix((lp.data, lp.indices, lp.indptr), shape=(lp.m, lp.n)), q=lp.q, c=lp.c, c0=lp.c0,
-                l=lp.l, u=lp.u, m_eq=lp.m_eq)
-
-
 @functools.lru_cache(maxsize=None)
 def _highs(T, J, variant):
     """HiGHS objectives of the (T, J, variant) windows, computed once."""
     out = []
     for lp in _lps(T, J, variant):
-        h = window_lp.solve_highs(_oracle(lp))
+        h = window_lp.solve_highs(from_window(lp))
         assert h["status"] == 0, (T, J, variant)
         out.append(h["obj"])
     return tuple(out)
@@ -69,11 +64,11 @@ def _within_bars(lps, res, objs):
     for k, (lp, r, ho) in enumerate(zip(lps, res, objs)):
         assert r.status == 0, (k, r.status_name)
         assert abs(r.obj - ho) <= 1e-5 * abs(ho), (k, r.obj, ho)
-        assert window_lp.primal_residual_rel(_oracle(lp), r.x)[0] <= 1e-6, k
+        assert window_lp.primal_residual_rel(from_window(lp), r.x)[0] <= 1e-6, k
 
 
 def _highs_objs(lps):
-    hs = [window_lp.solve_highs(_oracle(lp)) for lp in lps]
+    hs = [window_lp.solve_highs(from_window(lp)) for lp in lps]
     assert all(h["status"] == 0 for h in hs)
     return [h["obj"] for h in hs]
 

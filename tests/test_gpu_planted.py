@@ -15,6 +15,7 @@ because the host restatement itself misses that bar (the scale-spread windows).
 import numpy as np
 import pytest
 
+import band_cases as bc
 import planted_cases as pc
 import planted_lp
 import result_contract as rc
@@ -77,7 +78,7 @@ def test_planted_optimum_through_the_general_kernels(solver, name):
             and np.array_equal(r.y, res[0].y)
 
 
-LIMITS = (1, 2, 63, 64, 65, 127, 129)  # tests/test_gpu_band_loop.py's
+LIMITS = bc.LIMITS
 
 
 @pytest.mark.parametrize("name", ["small12_at", "ell24_22_at", "ell24_53_at", "gen22_lds", "gen53", "large4097"])

@@ -18,6 +18,7 @@ import functools
 import numpy as np
 import pytest
 
+import band_cases as bc
 import planted_cases as pc
 import planted_lp
 import result_contract as rc
@@ -29,8 +30,8 @@ pytestmark = pytest.mark.gpu
 
 OPTIONS = dict(eps=1e-6, eps_obj=1e-6, max_iters=100000, check_every=32, kkt_every=4, kkt_predict=0, warm_start=0,
                certify=0)
-BAND3, BAND3_J1, BAND1, ICE = 9002004, 9002054, 9000012, 9000112
-LIMITS = (1, 2, 63, 64, 65, 127, 129)  # tests/test_gpu_band_loop.py's: below, at and past one and two check periods
+BAND3, BAND3_J1, BAND1, ICE = bc.GENERIC, bc.STATIC, bc.ONE_STEP, bc.ICE
+LIMITS = bc.LIMITS  # below, at and past one and two check periods
 
 
 @pytest.fixture(scope="module")
