@@ -8,5 +8,7 @@ all-gather (``parallel.LibraryGather``).  There is no CPU fallback.
 """
 from .solver import BatchSolver, SolverError, WindowLP, WindowResult, version  # noqa: F401
 from .packed import PackedBatch, pack  # noqa: F401
+from .value_sizing import ValueSizingSpec, annuity_scalar, size_for_value  # noqa: F401
 
-__all__ = ["BatchSolver", "SolverError", "WindowLP", "WindowResult", "PackedBatch", "pack", "version"]
+__all__ = ["BatchSolver", "SolverError", "WindowLP", "WindowResult", "PackedBatch", "pack", "version", "ValueSizingSpec",
+           "annuity_scalar", "size_for_value"]

@@ -144,6 +144,27 @@ class ValuationArgs(ctypes.Structure):
 # DVH_BILL_ROWS, DVH_BILL_MAX_J, DVH_CBA_MAX_YEARS, DVH_CBA_MAX_EXTRA, DVH_CBA_FIXED_COLS, DVH_VALUE_COLS
 BILL_ROWS, BILL_MAX_J, CBA_MAX_YEARS, CBA_MAX_EXTRA, CBA_FIXED_COLS, VALUE_COLS = 8, 16, 64, 16, 7, 7
 
+class ValueSpec(ctypes.Structure):
+    """dvh_value_spec (economic sizing: what is sized for one case)."""
+    _fields_ = [("size_energy", ctypes.c_int32), ("size_power", ctypes.c_int32), ("c_energy", ctypes.c_double),
+                ("c_power", ctypes.c_double), ("c_fixed", ctypes.c_double), ("alpha", ctypes.c_double),
+                ("energy_min", ctypes.c_double), ("energy_max", ctypes.c_double), ("power_min", ctypes.c_double),
+                ("power_max", ctypes.c_double), ("gap_tol", ctypes.c_double), ("max_rounds", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+class ValueMasterArgs(ctypes.Structure):
+    """dvh_value_master_args (spec_host is a host array, every other pointer a device address)."""
+    _fields_ = [(f, ctypes.c_int32) for f in ("count", "n_cases", "W", "n_cand", "n_next", "cut_cap")] + \
+               [("spec_host", ctypes.POINTER(ValueSpec))] + \
+               [(f, ctypes.c_void_p) for f in ("spec", "case_ids", "window_cuts", "E_in", "P_in", "cuts", "state",
+                                               "flags", "E_out", "pch_out", "pdis_out")]
+
+
+# DVH_VALUE_CUT_COLS, DVH_VALUE_MAX_J, DVH_VALUE_MAX_CUTS, DVH_VALUE_MAX_CAND, DVH_VALUE_STATE_COLS, DVH_VALUE_FLAG_COLS
+VALUE_CUT_COLS, VALUE_MAX_J, VALUE_MAX_CUTS, VALUE_MAX_CAND, VALUE_STATE_COLS, VALUE_FLAG_COLS = 10, 64, 256, 8, 8, 8
+VALUE_STATUS_NAMES = {0: "SIZED", 1: "ROUND_LIMIT", 2: "LP_FAILED", 3: "MASTER_FAILED"}
+
 SYMBOLS = {
     "dvh_version": (ctypes.c_char_p, []),
     "dvh_default_options": (None, [ctypes.POINTER(Options)]),
@@ -202,6 +223,9 @@ SYMBOLS = {
     "dvh_value_scenarios": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ValuationArgs), ctypes.c_void_p,
                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "dvh_last_valuation_ms": (ctypes.c_int, [ctypes.c_void_p, c_double_p]),
+    "dvh_value_cuts": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(BatteryGroup), ctypes.POINTER(Packed),
+                                      ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
+    "dvh_value_master": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ValueMasterArgs), ctypes.c_void_p]),
     "dvh_comm_unique_id": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p]),
     "dvh_comm_init": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_char_p]),
     "dvh_comm_info": (ctypes.c_int, [ctypes.c_void_p, c_int32_p]),

@@ -16,8 +16,8 @@ LIB = os.path.join(HERE, "libdervet_hip.so")
 # does, and the GPU box refuses an exec from such a process)
 BUILDINFO = os.path.join(HERE, "libdervet_hip.buildinfo.json")
 SOURCES = ["dvh_kernels.hip", "dvh_band.hip", "dvh_band_persist.hip", "dvh_band_persist_ice.hip", "dvh_band_grid.hip", "dvh_chain.hip", "dvh_build.hip", "dvh_sweep.hip", "dvh_series.hip", "dvh_route.hip", "dvh_large.hip", "dvh_outage.hip",
-           "dvh_certify.hip", "dvh_sizing.hip", "dvh_degradation.hip", "dvh_valuation.hip", "dvh_api.cpp", "dvh_api_outage.cpp", "dvh_api_build.cpp",
-           "dvh_api_valuation.cpp", "dvh_solve.cpp",
+           "dvh_certify.hip", "dvh_sizing.hip", "dvh_degradation.hip", "dvh_valuation.hip", "dvh_value_sizing.hip", "dvh_api.cpp", "dvh_api_outage.cpp", "dvh_api_build.cpp",
+           "dvh_api_valuation.cpp", "dvh_api_value_sizing.cpp", "dvh_solve.cpp",
            "dvh_cascade.cpp", "dvh_validate.cpp", "dvh_comm.cpp", "dvh_sizing.cpp", "dvh_sizing_validate.cpp"]
 # per-source flags: the band kernel's persistent forms without machine-level loop-invariant code motion (their loop
 # invariants, hoisted out of the loop over windows, spilled; csrc/dvh_band_persist.hip), the battery form with the
@@ -30,12 +30,14 @@ EXTRA_FLAGS = {"dvh_band_persist.hip": ["-mllvm", "-disable-machine-licm", "-mll
                "dvh_kernels.hip": ["-mllvm", "-disable-machine-licm"],
                # the valuation kernels without contraction, so that host and device agree on every product and sum
                # (csrc/dvh_cba.h; its pragma covers clang, the flag says so on the command line)
-               "dvh_valuation.hip": ["-ffp-contract=off"]}
+               "dvh_valuation.hip": ["-ffp-contract=off"],
+               # the economic-sizing kernels likewise (csrc/dvh_value_cut.h)
+               "dvh_value_sizing.hip": ["-ffp-contract=off"]}
 INCLUDES = {"dvh_band_persist.hip": "dvh_band.hip",  # (a one-line source around another: its compile time)
             "dvh_band_persist_ice.hip": "dvh_band.hip"}
 # flags of every object (build() and build_variant()); bench.source_key() hashes them with EXTRA_FLAGS and the compiler
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-result", "-Wno-unused-value"]
-HEADERS = ["dvh_internal.h", "dvh_handle.h", "dvh_host.h", "dvh_device.h", "dvh_validate.h", "dvh_sizing_validate.h", "dvh_rng.h", "dvh_ziggurat.h", "dvh_rainflow.h", "dvh_degradation_validate.h", "dvh_cba.h", "dvh_valuation.h", "dvh_valuation_validate.h", os.path.join("..", "..", "include", "dervet_hip.h")]
+HEADERS = ["dvh_internal.h", "dvh_handle.h", "dvh_host.h", "dvh_device.h", "dvh_validate.h", "dvh_sizing_validate.h", "dvh_rng.h", "dvh_ziggurat.h", "dvh_rainflow.h", "dvh_degradation_validate.h", "dvh_cba.h", "dvh_valuation.h", "dvh_valuation_validate.h", "dvh_value_cut.h", "dvh_value_sizing.h", "dvh_value_sizing_validate.h", os.path.join("..", "..", "include", "dervet_hip.h")]
 
 
 def _stale():

@@ -622,6 +622,112 @@ int dvh_value_scenarios(dvh_handle* h, const dvh_valuation* v, double* values, i
  * 0 for one that has not run): ms2 = {bill, valuation}.  Waits for those two kernels. */
 int dvh_last_valuation_ms(const dvh_handle* h, double* ms2);
 
+/* ---- Economic sizing (ESSSizing.py:82-110, ContinuousSizing.sizing_objective, MicrogridScenario.py:208-217, 293-295
+ * with the annuity scalar of CBA.py:190-213; restated in dervet_hip/value_sizing.py): the energy and power rating that
+ * minimise lifetime cost
+ *   F(E, P) = c_energy E + c_power P + c_fixed + alpha sum_w V_w(E, P),
+ * V_w the optimum of the case's battery window w (dvh_build_battery_group's LP) at the rating E, pch = pdis = P, and
+ * c_energy = ccost_kwh, c_power = ccost_kw + alpha fixedOM, c_fixed = ccost.  Only the window's init / final right-hand
+ * sides (soc_target E), its ch / dis upper bounds (P) and its ene bounds (llsoc E, min(ulsoc E, emax_t)) depend on the
+ * rating, so V_w is convex and piecewise linear in it, and Kelley's cutting planes size the case: solve the windows at
+ * candidate ratings (dvh_solve_packed_device), cut (dvh_value_cuts), solve the master (dvh_value_master), repeat.
+ * Deviations from the reference: the integer sizes are relaxed and rounded up afterwards (lp.sizing.candidate), a sized
+ * quantity needs a finite box (the master must be bounded), has_ice and has_emin are DVH_ERR_UNSUPPORTED, and the charge
+ * and discharge ratings are one sized power: a window whose pch and pdis differ is refused by the cut pass (flag 4).
+ *
+ * The cut of a solved window at s = (E, P), from its returned y (>= rows clamped at 0): r = c - K'y, and by weak duality
+ *   V_w(s') >= D_w(s') = q(s')'y + sum_j [ l_j(s') r_j^+ - u_j(s') r_j^- ] + c0        for every s'
+ * (a term whose bound is infinite is dropped; rinf = the largest |r_j| pointing at one).  D_w is convex; linearised at s
+ * with the active piece of each ene bound:
+ *   g_E = soc_target (y_0 + y_T) + sum_t [ llsoc r_ene,t^+ - ulsoc r_ene,t^- (ulsoc E <= emax_t) ]
+ *   g_P = -sum_t (r_ch,t^- + r_dis,t^-),      a = D_w(s) - g_E E - g_P P,      theta_w >= a + g_E E' + g_P P'.
+ * The cut holds for any y, so a window that stopped at ITER_LIMIT still yields a valid one.
+ *
+ * dvh_value_cuts: the cuts of windows first .. first + G - 1 of a solved packed batch built from `group` (the same
+ * device arrays), one 256-thread workgroup per window; cuts_out[g][0 .. DVH_VALUE_CUT_COLS - 1] =
+ *   {a, g_E, g_P, D_w(s) (dual objective), c'x + c0 (primal objective), rinf, flag, window status, iterations, 0}.
+ * K'y is formed from the battery pattern's column structure, every CSR row checked against it on the device, and the
+ * demand-charge rows must come period by period with ascending steps (the builder's order); flag != 0 (1: the
+ * descriptor is not the group's shape or the window lies outside the arrays, 2: a row is not the pattern's, 4: pch !=
+ * pdis): the window was not read and the other columns are NaN.  Windows above 768 steps (the annual hourly window)
+ * keep their per-step demand-charge duals in a workspace of the handle, allocated on their first use.  No
+ * floating-point atomics, fixed-order reductions: bit-identical run to run, to the host restatement
+ * (csrc/dvh_value_cut.h) and whatever else the batch holds.  Asynchronous on `stream` (a hipStream_t; NULL = the
+ * handle's stream, i.e. after its solves).  DVH_ERR_UNSUPPORTED: has_ice, has_emin, J above DVH_VALUE_MAX_J. */
+#define DVH_VALUE_CUT_COLS 10
+#define DVH_VALUE_MAX_J 64
+#define DVH_VALUE_MAX_CUTS 256
+#define DVH_VALUE_MAX_CAND 8
+int dvh_value_cuts(dvh_handle* h, const dvh_battery_group* group, const dvh_packed* batch, int32_t first,
+                   double* cuts_out, void* stream);
+
+/* What is sized for one case (a sized quantity: its box, finite; a rating that is not sized: min = max = the rating). */
+typedef struct dvh_value_spec {
+  int32_t size_energy, size_power; /* at least one                                                                  */
+  double c_energy, c_power;        /* $/kWh, $/kW (ccost_kw + alpha fixedOM); > 0 for a sized quantity              */
+  double c_fixed;                  /* $                                                                             */
+  double alpha;                    /* annuity scalar, > 0                                                           */
+  double energy_min, energy_max;   /* kWh                                                                           */
+  double power_min, power_max;     /* kW                                                                            */
+  double gap_tol;                  /* stop at upper - lower <= gap_tol (1 + |upper|); > 0                           */
+  int32_t max_rounds, reserved;    /* 1 .. 65536                                                                    */
+} dvh_value_spec;
+
+#define DVH_VALUE_SIZED 0
+#define DVH_VALUE_ROUND_LIMIT 1   /* max_rounds rounds done, or the cut list is full                                */
+#define DVH_VALUE_LP_FAILED 2     /* a candidate's window did not come back OPTIMAL (e.g. sdr > 0 at P = 0):        */
+                                  /* flags[DVH_VF_LP_STATUS] = that window's status, -1 for a flagged cut           */
+#define DVH_VALUE_MASTER_FAILED 3 /* the master solve did not end (flags[DVH_VF_MASTER]; not observed)              */
+/* state[case][DVH_VALUE_STATE_COLS] (doubles) and flags[case][DVH_VALUE_FLAG_COLS] (int32), device arrays the caller
+ * initialises: state = {-inf, +inf, 0, ...}, flags = 0. */
+#define DVH_VALUE_STATE_COLS 8
+#define DVH_VS_LOWER 0  /* best master optimum + c_fixed                                                            */
+#define DVH_VS_UPPER 1  /* best F at a candidate, from the windows' primal objectives                               */
+#define DVH_VS_INC_E 2  /* the incumbent: the candidate of `upper`                                                  */
+#define DVH_VS_INC_P 3
+#define DVH_VS_INC_V 4  /* its sum_w V_w                                                                            */
+#define DVH_VS_Z_E 5    /* the last master optimum                                                                  */
+#define DVH_VS_Z_P 6
+#define DVH_VS_THETA 7
+#define DVH_VALUE_FLAG_COLS 8
+#define DVH_VF_DONE 0
+#define DVH_VF_STATUS 1
+#define DVH_VF_LP_STATUS 2
+#define DVH_VF_NCUTS 3
+#define DVH_VF_ROUNDS 4
+#define DVH_VF_LP_ITERS 5
+#define DVH_VF_MASTER 6
+
+/* One round's master step for `count` cases, one wave per case.  Case k of the call is case case_ids[k] of the
+ * n_cases the per-case arrays hold; its windows were solved at n_cand candidates, and window_cuts[p][k][j][.] is
+ * dvh_value_cuts' record of window position p (W positions) of candidate j, whose rating is E_in / P_in [k][j].  Per
+ * case: the candidates' cuts summed over the positions in position order and appended to cuts[case][.][3] (cut_cap
+ * rows, <= DVH_VALUE_MAX_CUTS); upper / the incumbent updated from F at each candidate; the master
+ *   min c_energy E + c_power P + alpha theta   s.t.  theta >= a_k + gE_k E + gP_k P,  E, P in their boxes
+ * solved exactly (a dual simplex on three-constraint bases, deterministic); lower = max(lower, its optimum + c_fixed);
+ * done with DVH_VALUE_SIZED when upper - lower <= gap_tol (1 + |upper|), with DVH_VALUE_ROUND_LIMIT after max_rounds
+ * rounds or when the next round's cuts would not fit, with DVH_VALUE_LP_FAILED when a candidate's window is not
+ * OPTIMAL; else the next round's n_next candidates -- the master optimum z*, then inc + (j / n_next)(z* - inc),
+ * j = 1 .. n_next - 1, inc the incumbent -- written to E_out / pch_out / pdis_out [k][j], the arrays the builder reads
+ * (they may be E_in / P_in themselves only when n_next = n_cand).  A case already done is left as it is.
+ * spec_host is validated before the launch and must equal the device copy `spec`.  Asynchronous on `stream`. */
+typedef struct dvh_value_master_args {
+  int32_t count, n_cases, W, n_cand, n_next, cut_cap;
+  const dvh_value_spec* spec_host; /* host [n_cases]                                                                */
+  const dvh_value_spec* spec;      /* [n_cases] the same on the device                                              */
+  const int32_t* case_ids;         /* [count]                                                                       */
+  const double* window_cuts;       /* [W][count][n_cand][DVH_VALUE_CUT_COLS]                                        */
+  const double* E_in;              /* [count][n_cand]                                                               */
+  const double* P_in;              /* [count][n_cand]                                                               */
+  double* cuts;                    /* [n_cases][cut_cap][3]                                                         */
+  double* state;                   /* [n_cases][DVH_VALUE_STATE_COLS]                                               */
+  int32_t* flags;                  /* [n_cases][DVH_VALUE_FLAG_COLS]                                                */
+  double* E_out;                   /* [count][n_next]                                                               */
+  double* pch_out;                 /* [count][n_next]                                                               */
+  double* pdis_out;                /* [count][n_next]                                                               */
+} dvh_value_master_args;
+int dvh_value_master(dvh_handle* h, const dvh_value_master_args* args, void* stream);
+
 /* Kernel cascade (testing / A-B timing): 0 = default (battery-banded -> ELL -> generic CSR), 1 = generic
  * CSR kernel for every window, 2 = ELL -> generic (no battery-banded kernel), 3 / 4 = as 0 with the battery-banded
  * kernel's form forced: one step per lane (768 threads per window, one window per CU) / three steps per lane (256
