@@ -1,34 +1,15 @@
 // dvh_api.cpp -- C ABI of libdervet_hip (declared in include/dervet_hip.h): the handle's lifetime, options, setters
 // and dvh_last_* getters, and the communicator wrappers.  The solves are in dvh_solve.cpp (tier drivers:
-// dvh_cascade.cpp), the other entry points in dvh_api_build.cpp, dvh_api_outage.cpp and dvh_sizing.cpp.
+// dvh_cascade.cpp), the other entry points in dvh_api_build.cpp, dvh_api_outage.cpp, dvh_api_valuation.cpp,
+// dvh_api_value_sizing.cpp and dvh_sizing.cpp.  The handle owns whatever any of them makes (dvh_handle.h): dvh_destroy
+// selects the device, waits on the stream and deletes it.
 #include "dvh_handle.h"
 
 #define DVH_VERSION_STRING "dervet_hip 0.1.0 (gfx950, restarted reflected-Halpern PDHG)"
 
 namespace dvh {
-HandleView handle_view(dvh_handle* h) { return HandleView{h->device, h->stream, &h->opts, &h->err, &h->sizing}; }
+HandleView handle_view(dvh_handle* h) { return HandleView{h->device, h->stream, &h->opts, &h->err, &h->sizing.p}; }
 }  // namespace dvh
-
-// Teardown, after dvh_destroy has selected the device and waited on the stream: the pinned host words here, then the
-// members (every device buffer), then the base: events, large / comm / sizing, the stream last.
-dvh_handle::~dvh_handle() {
-  if (route_host) hipHostFree(route_host);
-  if (cert_host) hipHostFree(cert_host);
-}
-
-dvh_handle_core::~dvh_handle_core() {
-  for (auto& e : cert_ev)
-    if (e) hipEventDestroy(e);
-  for (auto& e : ev)
-    if (e) hipEventDestroy(e);
-  for (auto& ce : chunk_events)
-    for (hipEvent_t e : ce)
-      if (e) hipEventDestroy(e);
-  if (large) dvh::large_destroy(large);
-  if (comm) dvh::comm_destroy(comm);
-  if (sizing) dvh::sizing_destroy(sizing);
-  if (stream) hipStreamDestroy(stream);
-}
 
 extern "C" {
 
@@ -119,7 +100,11 @@ static int create_one(int dev, const dvh_options* opts, dvh_handle** out) {
     delete h;
     return DVH_ERR_HIP;
   }
-  for (auto& e : h->ev) hipEventCreate(&e);
+  for (DevEvent& e : h->ev)
+    if (e.ensure() != hipSuccess) {
+      dvh_destroy(h);
+      return DVH_ERR_HIP;
+    }
   {  // Halpern weight table 1/(k+2): exact IEEE quotients, identical to the host restatement
     std::vector<double> tab(dvh::kHalpernTab);
     for (int k = 0; k < dvh::kHalpernTab; ++k) tab[k] = 1.0 / (k + 2.0);
@@ -150,7 +135,7 @@ int dvh_destroy(dvh_handle* h) {
   h->peers.clear();
   hipSetDevice(h->device);
   if (h->stream) hipStreamSynchronize(h->stream);
-  delete h;  // ~dvh_handle: buffers and pinned words, events, large / comm / sizing, the stream
+  delete h;  // pinned words, buffers, events, large / comm / sizing, the stream (dvh_handle.h)
   return DVH_OK;
 }
 
@@ -178,7 +163,7 @@ int dvh_comm_info(const dvh_handle* h, int32_t* rank_world) {
     return DVH_OK;
   }
   int r = 0, w = 0;
-  dvh::comm_info(h->comm, &r, &w);
+  dvh::comm_info(h->comm.get(), &r, &w);
   rank_world[0] = r;
   rank_world[1] = w;
   return DVH_OK;
@@ -190,7 +175,7 @@ int dvh_gather_results(dvh_handle* h, const void* rows, uint64_t bytes_per_rank,
   if (bytes_per_rank == 0) return DVH_OK;
   hipSetDevice(h->device);
   hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-  return dvh::comm_all_gather(h->comm, rows, out, (size_t)bytes_per_rank, s, &h->err);
+  return dvh::comm_all_gather(h->comm.get(), rows, out, (size_t)bytes_per_rank, s, &h->err);
 }
 const char* dvh_last_warning(const dvh_handle* h) { return h ? h->st.warn.c_str() : "null handle"; }
 

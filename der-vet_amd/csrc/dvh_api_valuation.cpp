@@ -1,59 +1,25 @@
 // dvh_api_valuation.cpp -- the scenario valuation's entry points (dvh_valuation.hip): dvh_bill_windows,
 // dvh_value_scenarios, dvh_last_valuation_ms.  Both calls validate on the host (dvh_valuation_validate.h), then launch
-// one kernel between two timing events on the caller's stream: no wait, no device allocation.
-#include <mutex>
-#include <unordered_map>
-
+// one kernel between two of the handle's timing events (dvh_handle.h val_ev, created by a call's first run) on the
+// caller's stream: no wait, no device allocation.
 #include "dvh_handle.h"
 #include "dvh_valuation.h"
 #include "dvh_valuation_validate.h"
 
 namespace {
 
-// The two calls' timing events, per handle.  Kept beside the handle rather than in it: created by a handle's first
-// valuation call on its device and reused by every later one.  dvh_destroy does not know them, so they live until the
-// process ends (four events per handle that ever valued); a new handle at a destroyed one's address takes them over,
-// re-created when it sits on another device.
-struct ValTimers {
-  int device = -1;
-  hipEvent_t ev[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};  // {bill, valuation} x {start, stop}
-  bool ran[2] = {false, false};
-};
-std::mutex g_mu;
-std::unordered_map<const dvh_handle*, ValTimers> g_timers;
-
-hipError_t timers_for(dvh_handle* h, ValTimers** out) {
-  ValTimers& t = g_timers[h];
-  if (t.device != h->device) {
-    for (auto& pair : t.ev)
-      for (hipEvent_t& e : pair) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-        hipError_t r = hipEventCreate(&e);
-        if (r != hipSuccess) {
-          t.device = -1;
-          return r;
-        }
-      }
-    t.device = h->device;
-    t.ran[0] = t.ran[1] = false;
-  }
-  *out = &t;
-  return hipSuccess;
-}
-
 // launch() between the events of call `which` on stream s
 template <class F>
 int timed_launch(dvh_handle* h, int which, hipStream_t s, const char* name, F launch) {
-  std::lock_guard<std::mutex> lock(g_mu);
-  ValTimers* t = nullptr;
+  DevEvent* ev = h->val_ev[which];
   DVH_HIP(h, hipSetDevice(h->device));
-  DVH_HIP(h, timers_for(h, &t));
-  DVH_HIP(h, hipEventRecord(t->ev[which][0], s));
+  DVH_HIP(h, ev[0].ensure());
+  DVH_HIP(h, ev[1].ensure());
+  DVH_HIP(h, hipEventRecord(ev[0], s));
   hipError_t e = launch();
   if (e != hipSuccess) return hip_fail(h, e, name);
-  DVH_HIP(h, hipEventRecord(t->ev[which][1], s));
-  t->ran[which] = true;
+  DVH_HIP(h, hipEventRecord(ev[1], s));
+  h->val_ran[which] = true;
   return DVH_OK;
 }
 
@@ -87,15 +53,12 @@ extern "C" int dvh_value_scenarios(dvh_handle* h, const dvh_valuation* v, double
 extern "C" int dvh_last_valuation_ms(const dvh_handle* h, double* ms2) {
   if (!h || !ms2) return DVH_ERR_ARG;
   ms2[0] = ms2[1] = 0.0;
-  std::lock_guard<std::mutex> lock(g_mu);
-  auto it = g_timers.find(h);
-  if (it == g_timers.end() || it->second.device != h->device) return DVH_OK;
   dvh_handle* hm = const_cast<dvh_handle*>(h);
   for (int k = 0; k < 2; ++k) {
-    if (!it->second.ran[k]) continue;
+    if (!h->val_ran[k]) continue;
     float ms = 0.0f;
-    DVH_HIP(hm, hipEventSynchronize(it->second.ev[k][1]));
-    DVH_HIP(hm, hipEventElapsedTime(&ms, it->second.ev[k][0], it->second.ev[k][1]));
+    DVH_HIP(hm, hipEventSynchronize(h->val_ev[k][1]));
+    DVH_HIP(hm, hipEventElapsedTime(&ms, h->val_ev[k][0], h->val_ev[k][1]));
     ms2[k] = ms;
   }
   return DVH_OK;

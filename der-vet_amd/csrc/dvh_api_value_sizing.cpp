@@ -1,10 +1,7 @@
 // dvh_api_value_sizing.cpp -- the economic sizing's entry points (dvh_value_sizing.hip): dvh_value_cuts,
 // dvh_value_master.  Both validate on the host (dvh_value_sizing_validate.h), then launch one kernel on the caller's
-// stream: no wait.  The only device allocation is the cut pass's workspace for windows above the LDS size.
-#include <memory>
-#include <mutex>
-#include <unordered_map>
-
+// stream: no wait.  The only device allocation is the cut pass's workspace for windows above the LDS size, the
+// handle's v_zwork (dvh_handle.h): grown on demand and freed by dvh_destroy.
 #include "dvh_handle.h"
 #include "dvh_value_sizing.h"
 #include "dvh_value_sizing_validate.h"
@@ -12,16 +9,6 @@
 namespace {
 
 constexpr int kLdsT = 768;  // value_cut_kernel keeps z in LDS up to here
-
-// The cut pass's workspace, per handle.  Kept beside the handle rather than in it (as the valuation's timing events
-// are): allocated by a handle's first long-window call on its device, grown on demand, and alive until the process
-// ends; a new handle at a destroyed one's address takes it over, re-allocated when it sits on another device.
-struct CutWork {
-  int device = -1;
-  DevBuf z;
-};
-std::mutex g_mu;
-std::unordered_map<const dvh_handle*, std::unique_ptr<CutWork>> g_work;
 
 }  // namespace
 
@@ -53,21 +40,14 @@ extern "C" int dvh_value_cuts(dvh_handle* h, const dvh_battery_group* group, con
   a.first = first;
   a.out = cuts_out;
   a.zwork = nullptr;
-  std::lock_guard<std::mutex> lock(g_mu);
   if (group->T > kLdsT) {
-    std::unique_ptr<CutWork>& w = g_work[h];
-    if (!w) w.reset(new CutWork);
-    if (w->device != h->device) {
-      w->z.release();
-      w->device = h->device;
-    }
     const size_t want = sizeof(double) * (size_t)group->G * (size_t)group->T;
-    if (want > w->z.bytes) {
+    if (want > h->v_zwork.bytes) {
       // a launch in flight may still use the old buffer: wait for it before the buffer is replaced
       DVH_HIP(h, hipStreamSynchronize(s));
-      DVH_HIP(h, w->z.ensure(want));
+      DVH_HIP(h, h->v_zwork.ensure(want));
     }
-    a.zwork = w->z.as<double>();
+    a.zwork = h->v_zwork.as<double>();
   }
   hipError_t e = dvh::launch_value_cuts(a, s);
   if (e != hipSuccess) return hip_fail(h, e, "value_cut_kernel");

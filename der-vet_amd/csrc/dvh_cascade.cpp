@@ -171,7 +171,7 @@ int device_cascade(dvh_handle* h, const dvh::Batch& b, const dvh::Work& w, const
   int32_t* L[5];
   for (int r = 0; r < 5; ++r) L[r] = h->d_list.as<int32_t>() + (size_t)r * wc;
   int32_t* info = h->d_route.as<int32_t>();  // 8 ints per route: {count, wx, wy, max n, max m, max nnz}
-  int32_t* rh = h->route_host;
+  int32_t* rh = h->route_host.as<int32_t>();
   if (h->cus <= 0 && hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess)
     h->cus = 256;
   // band kernel form: three steps per lane (two windows per CU) once the windows outnumber the CUs; a window alone

@@ -102,7 +102,7 @@ int comm_unique_id(unsigned char* id, std::string* err) {
   return DVH_OK;
 }
 
-int comm_init(int device, int rank, int world, const unsigned char* id, Comm** out, std::string* err) {
+int comm_init(int device, int rank, int world, const unsigned char* id, CommOwner* out, std::string* err) {
   const RcclApi& a = rccl();
   if (!a.lib) {
     *err = a.err;
@@ -124,7 +124,7 @@ int comm_init(int device, int rank, int world, const unsigned char* id, Comm** o
     delete c;
     return DVH_ERR_HIP;
   }
-  *out = c;
+  out->reset(c);
   return DVH_OK;
 }
 

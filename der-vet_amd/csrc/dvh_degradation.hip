@@ -121,11 +121,6 @@ hipError_t launch_rainflow(const DegArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
-int fail(const HandleView& v, int code, const std::string& msg) {
-  *v.err = msg;
-  return code;
-}
-
 }  // namespace
 }  // namespace dvh
 
@@ -140,8 +135,7 @@ extern "C" int dvh_cycle_damage(dvh_handle* h, const double* ene, int64_t row_st
     return dvh::fail(v, DVH_ERR_UNSUPPORTED, "cycle damage: T = " + std::to_string(T) + " steps do not fit a workgroup's "
                      "LDS (at most " + std::to_string(dvh::kRainflowMaxT) + ")");
   if (S == 0) return DVH_OK;
-  hipError_t e = hipSetDevice(v.device);
-  if (e != hipSuccess) return dvh::fail(v, DVH_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+  DVH_VIEW_HIP(v, hipSetDevice(v.device));
   dvh::DegArgs a{};
   a.ene = ene;
   a.row_stride = row_stride;
@@ -152,7 +146,7 @@ extern "C" int dvh_cycle_damage(dvh_handle* h, const double* ene, int64_t row_st
   a.life = life;
   a.e_rated = e_rated;
   a.damage_out = damage_out;
-  e = dvh::launch_rainflow(a, stream ? (hipStream_t)stream : v.stream);
+  hipError_t e = dvh::launch_rainflow(a, stream ? (hipStream_t)stream : v.stream);
   if (e != hipSuccess) return dvh::fail(v, DVH_ERR_HIP, std::string("rainflow_kernel: ") + hipGetErrorString(e));
   return DVH_OK;
 }
@@ -170,13 +164,12 @@ extern "C" int dvh_degradation_update(dvh_handle* h, const dvh_packed* batch, in
     return dvh::fail(v, DVH_ERR_UNSUPPORTED, "degradation update: T = " + std::to_string(T) + " steps do not fit a "
                      "workgroup's LDS (at most " + std::to_string(dvh::kRainflowMaxT) + ")");
   if (S == 0) return DVH_OK;
-  hipError_t e = hipSetDevice(v.device);
-  if (e != hipSuccess) return dvh::fail(v, DVH_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+  DVH_VIEW_HIP(v, hipSetDevice(v.device));
   hipStream_t s = stream ? (hipStream_t)stream : v.stream;
   if (!state->incl_cycle_degrade) {
     hipLaunchKernelGGL(dvh::degradation_off_kernel, dim3((S + dvh::kDegB - 1) / dvh::kDegB), dim3(dvh::kDegB), 0, s,
                        *state, S);
-    e = hipGetLastError();
+    hipError_t e = hipGetLastError();
     if (e != hipSuccess) return dvh::fail(v, DVH_ERR_HIP, std::string("degradation_off_kernel: ") + hipGetErrorString(e));
     return DVH_OK;
   }
@@ -196,7 +189,7 @@ extern "C" int dvh_degradation_update(dvh_handle* h, const dvh_packed* batch, in
   a.st = *state;
   a.days = days;
   a.eol = eol_condition;
-  e = dvh::launch_rainflow(a, s);
+  hipError_t e = dvh::launch_rainflow(a, s);
   if (e != hipSuccess) return dvh::fail(v, DVH_ERR_HIP, std::string("rainflow_kernel: ") + hipGetErrorString(e));
   return DVH_OK;
 }

@@ -41,23 +41,42 @@ struct SolveStats {
   }
 };
 
-// What must outlive the device buffers at teardown.  A base of the handle, so that its destructor runs after every
-// member's: events, then large / comm / sizing, the stream last (dvh_api.cpp).
+// The stream, in a base of the handle so that it goes after every member.
 struct dvh_handle_core {
   int device = 0;
   hipStream_t stream = nullptr;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  hipEvent_t cert_ev[2] = {nullptr, nullptr};  // the certificate pass's events
-  // per-chunk timing events: a pool created on first use and reused by every solve (destroyed with the handle), so
-  // no exit path of a solve can leak them; st.chunk_used = the events of the last solve
-  std::vector<std::array<hipEvent_t, 3>> chunk_events;
-  dvh::LargeSolver* large = nullptr;  // grid-wide path for windows above dvh::kSmallMax (created on first use)
-  dvh::Comm* comm = nullptr;  // dvh_comm_init: the result all-gather's RCCL communicator (dvh_comm.cpp)
-  dvh::SizingState* sizing = nullptr;  // reliability sizing (dvh_sizing.cpp): device buffers, last call's timing
-  ~dvh_handle_core();
+  ~dvh_handle_core() {
+    if (stream) (void)hipStreamDestroy(stream);
+  }
 };
 
+// The sizing state's owner.  A plain pointer inside, not a std::unique_ptr as large and comm are: dvh_sizing.cpp fills
+// it through HandleView::sizing, a SizingState**, which the sanitizer driver's stand-in handle provides as well.
+struct SizingSlot {
+  dvh::SizingState* p = nullptr;
+  SizingSlot() = default;
+  SizingSlot(const SizingSlot&) = delete;
+  SizingSlot& operator=(const SizingSlot&) = delete;
+  ~SizingSlot() {
+    if (p) dvh::sizing_destroy(p);
+  }
+};
+
+// Everything a handle ever makes is a member that frees itself, so dvh_destroy (select the device, wait on the stream,
+// delete) releases all of it.  Members go in reverse order of declaration: the pinned words (declared last), the
+// device buffers, the events, large / comm / sizing, then the base's stream.
 struct dvh_handle : dvh_handle_core {
+  SizingSlot sizing;        // reliability sizing (dvh_sizing.cpp): device buffers, last call's timing
+  dvh::CommOwner comm;      // dvh_comm_init: the result all-gather's RCCL communicator (dvh_comm.cpp)
+  dvh::LargeOwner large;    // grid-wide path for windows above dvh::kSmallMax (created on first use)
+  DevEvent ev[4];           // a solve's (an outage sweep's) first and last event: [0], [3]
+  DevEvent cert_ev[2];      // the certificate pass's events
+  // per-chunk timing events: a pool created on first use and reused by every solve (destroyed with the handle), so
+  // no exit path of a solve can leak them; st.chunk_used = the events of the last solve
+  std::vector<std::array<DevEvent, 3>> chunk_events;
+  // scenario valuation (dvh_api_valuation.cpp): {bill, valuation} x {start, stop}, created by a call's first run
+  DevEvent val_ev[2][2];
+  bool val_ran[2] = {false, false};
   dvh_options opts{};
   std::string err;
   // packed inputs / outputs for the host API
@@ -76,12 +95,10 @@ struct dvh_handle : dvh_handle_core {
   DevBuf s_pairs, s_wts, s_bad;                   // seeded-sweep warm transfer (dvh_sweep.hip)
   DevBuf g_seeds, g_word;                         // scenario series generator (dvh_series.hip)
   DevBuf d_route;                                 // cascade lists' counts / ELL widths (dvh_route.hip)
-  int32_t* route_host = nullptr;                  // their pinned host mirror (one small read-back per tier)
-  // certificate pass (dvh_certify.hip): its workspace (allocated on first use), the device counters and their pinned
-  // host mirror (copied behind the pass, read at the solve's final wait)
+  // certificate pass (dvh_certify.hip): its workspace (allocated on first use) and the device counters
   DevBuf c_tptr, c_tind, c_tval, c_tau, c_gx, c_sig, c_gy, c_counts;
-  int32_t* cert_host = nullptr;
   bool cert_pending = false;
+  DevBuf v_zwork;  // economic sizing's cut pass (dvh_api_value_sizing.cpp): z of the windows above the LDS size, G * T
   int n_syncs = 0;                                // host waits on the stream in the last solve
   double outage_ms = 0.0;
   int last_variant = -1;
@@ -97,7 +114,9 @@ struct dvh_handle : dvh_handle_core {
   // host-buffer batch is split into contiguous, cost-balanced ranges, one per device, solved concurrently (one host
   // thread per device, no inter-device traffic), results written straight into the caller's buffers.
   std::vector<dvh_handle*> peers;
-  ~dvh_handle();  // the pinned host words; the buffers follow, then the base (dvh_api.cpp)
+  // pinned host mirrors: d_route's (one small read-back per tier) and c_counts' (copied behind the certificate pass,
+  // read at the solve's final wait)
+  PinnedBuf route_host, cert_host;
 };
 
 // Every host wait on a solve's stream goes through here (dvh_last_host_syncs reports the count of the last solve).

@@ -1,6 +1,8 @@
-// dvh_host.h -- what the host units share that needs no handle: the device buffer and the outage staging.  Apart from
-// dvh_handle.h so that dvh_sizing.cpp, which reaches the handle through dvh::HandleView, builds into the sanitizer
-// driver beside that driver's stand-in handle (tests/native/sizing_sanitize.cpp).  Host only, header only.
+// dvh_host.h -- what the host units share that needs no handle: the owners of a device buffer, an event and a pinned
+// host buffer, and the outage staging.  Apart from dvh_handle.h so that dvh_sizing.cpp, which reaches the handle through
+// dvh::HandleView, builds into the sanitizer driver beside that driver's stand-in handle
+// (tests/native/sizing_sanitize.cpp); dvh_large.hip includes it for its solver's host state.  Host only, header only
+// (tests/native/owner_sanitize.cpp drives the three owners against counting stand-ins of the HIP calls they make).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -12,8 +14,7 @@
 #include "dvh_internal.h"
 
 // Grow-only device buffer, freed with its owner.  slack_div: a growth asks for want / slack_div bytes more (0: exactly
-// what is asked; the sizing state's buffers take 4, their LPs grow by one window per round).  (dvh_large.hip keeps a
-// copy of its own, `Buf`.)
+// what is asked; the sizing state's buffers take 4, their LPs grow by one window per round).
 struct DevBuf {
   void* p = nullptr;
   size_t bytes = 0;
@@ -28,12 +29,71 @@ struct DevBuf {
     want = std::max<size_t>(want + (slack_div ? want / slack_div : 0), 256);
     hipError_t e = hipMalloc(&p, want);
     if (e == hipSuccess) bytes = want;
+    else p = nullptr;
     return e;
   }
   void release() {
     if (p) (void)hipFree(p);
     p = nullptr;
     bytes = 0;
+  }
+  template <class T>
+  T* as() const { return static_cast<T*>(p); }
+};
+
+// Event, created by the first ensure() on the current device (flags: hipEventDisableTiming for one that only orders)
+// and destroyed with its owner.  Move-only, so that arrays of them may sit in a std::vector (the handle's chunk-event
+// pool); a failed ensure() leaves it empty.
+struct DevEvent {
+  hipEvent_t e = nullptr;
+  DevEvent() = default;
+  DevEvent(DevEvent&& o) noexcept : e(o.e) { o.e = nullptr; }
+  DevEvent& operator=(DevEvent&& o) noexcept {
+    if (this != &o) {
+      release();
+      e = o.e;
+      o.e = nullptr;
+    }
+    return *this;
+  }
+  ~DevEvent() { release(); }
+  hipError_t ensure(unsigned flags = hipEventDefault) {
+    if (e) return hipSuccess;
+    hipError_t r = hipEventCreateWithFlags(&e, flags);
+    if (r != hipSuccess) e = nullptr;
+    return r;
+  }
+  void release() {
+    if (e) (void)hipEventDestroy(e);
+    e = nullptr;
+  }
+  operator hipEvent_t() const { return e; }
+};
+
+// Pinned host words, the landing place of a small read-back: allocated by the first ensure(), whose size they keep,
+// and freed with their owner.  Move-only; a failed ensure() leaves it empty.
+struct PinnedBuf {
+  void* p = nullptr;
+  PinnedBuf() = default;
+  PinnedBuf(PinnedBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
+  PinnedBuf& operator=(PinnedBuf&& o) noexcept {
+    if (this != &o) {
+      release();
+      p = o.p;
+      o.p = nullptr;
+    }
+    return *this;
+  }
+  ~PinnedBuf() { release(); }
+  hipError_t ensure(size_t bytes) {
+    if (p) return hipSuccess;
+    hipError_t r = hipHostMalloc(&p, bytes, hipHostMallocDefault);
+    if (r != hipSuccess) p = nullptr;
+    return r;
+  }
+  void release() {
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
   }
   template <class T>
   T* as() const { return static_cast<T*>(p); }

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <memory>
 #include <string>
 
 struct dvh_window_series;  // include/dervet_hip.h
@@ -240,33 +241,49 @@ hipError_t launch_build_sizing(const SizingLP* d_lps, int nlp, const int64_t* de
 hipError_t launch_gather_sizes(const int64_t* desc, const double* x, const int32_t* istats, int nlp, double* sizes,
                                hipStream_t s);
 
+// The handle's opaque sub-objects, each defined and destroyed by its own unit: the handle holds them as owners.
+struct SizingState;  // reliability sizing (dvh_sizing.cpp)
+void sizing_destroy(SizingState* s);
+struct LargeSolver;  // grid-wide PDHG for one window too large for the workgroup-per-window kernels (dvh_large.hip)
+LargeSolver* large_create();
+void large_destroy(LargeSolver* ls);
+struct Comm;  // the result all-gather's RCCL communicator (dvh_comm.cpp)
+void comm_destroy(Comm* c);
+template <auto Destroy>
+struct DestroyWith {
+  template <class T>
+  void operator()(T* p) const { Destroy(p); }
+};
+using LargeOwner = std::unique_ptr<LargeSolver, DestroyWith<large_destroy>>;
+using CommOwner = std::unique_ptr<Comm, DestroyWith<comm_destroy>>;
+
 // What dvh_sizing.cpp and dvh_degradation.hip need of a handle (the other host units include dvh_handle.h;
 // handle_view is in dvh_api.cpp, and the sizing sanitizer driver has a stand-in).
-struct SizingState;
 struct HandleView {
   int device;
   hipStream_t stream;
   dvh_options* opts;
   std::string* err;
-  SizingState** sizing;  // owned by the handle, freed by sizing_destroy at dvh_destroy
+  SizingState** sizing;  // the handle's (freed by sizing_destroy with it), created by the first sizing call
 };
 HandleView handle_view(dvh_handle* h);
-void sizing_destroy(SizingState* s);
+inline int fail(const HandleView& v, int code, const std::string& msg) {
+  *v.err = msg;
+  return code;
+}
+#define DVH_VIEW_HIP(v, call)                                                                                  \
+  do {                                                                                                         \
+    hipError_t e_ = (call);                                                                                    \
+    if (e_ != hipSuccess) return dvh::fail(v, DVH_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
+  } while (0)
 
-// Grid-wide PDHG for one window too large for the workgroup-per-window kernels (dvh_large.hip).
-struct LargeSolver;
-LargeSolver* large_create();
-void large_destroy(LargeSolver* ls);
 
-// The result all-gather's RCCL communicator (dvh_comm.cpp; dvh_comm_init / dvh_gather_results).  Return codes are the
-// DVH_* codes; messages go to *err.
+// The communicator's calls (dvh_comm_init / dvh_gather_results).  Return codes are the DVH_* codes; messages go to *err.
 constexpr int kCommIdBytes = 128;  // ncclUniqueId
-struct Comm;
 int comm_unique_id(unsigned char* id, std::string* err);
-int comm_init(int device, int rank, int world, const unsigned char* id, Comm** out, std::string* err);
+int comm_init(int device, int rank, int world, const unsigned char* id, CommOwner* out, std::string* err);
 int comm_all_gather(Comm* c, const void* send, void* recv, size_t bytes, hipStream_t s, std::string* err);
 void comm_info(const Comm* c, int* rank, int* world);
-void comm_destroy(Comm* c);
 // Solves window k (desc row d) of the batch on stream s; writes b.x / b.y / b.stats / b.istats of window k.
 hipError_t large_solve(LargeSolver* ls, const Batch& b, int k, const int64_t* d, const Opts& o, const double* hinv,
                        hipStream_t s, std::string* err, float* setup_ms, float* pdhg_ms);

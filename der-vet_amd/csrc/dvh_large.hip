@@ -26,7 +26,7 @@
 #include <string>
 #include <vector>
 
-#include "dvh_internal.h"
+#include "dvh_host.h"
 
 namespace dvh {
 namespace {
@@ -593,39 +593,17 @@ __global__ __launch_bounds__(LB) void lg_finish(LgArgs a) {
   }
 }
 
-struct Buf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  hipError_t ensure(size_t want) {
-    want = std::max<size_t>(want, 256);
-    if (want <= bytes) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
-    hipError_t e = hipMalloc(&p, want);
-    if (e == hipSuccess) bytes = want;
-    return e;
-  }
-  template <class T>
-  T* as() const { return static_cast<T*>(p); }
-};
-
 }  // namespace
 
+// The solver's host state (the owners of dvh_host.h).  No request below is for 0 bytes -- the int arena holds at
+// least its 64 flag words, the double arena 20 padded blocks -- so every buffer is non-null after its ensure().
 struct LargeSolver {
-  Buf ints, dbls, st;
-  int32_t* pinned_status = nullptr;
+  DevBuf ints, dbls, st;
+  PinnedBuf pinned_status;
   hipStream_t cap = nullptr;  // graph-capture stream (capture never executes work)
-  hipEvent_t poll[2] = {nullptr, nullptr};
-  hipEvent_t tev[3] = {nullptr, nullptr, nullptr};  // setup / PDHG timing brackets, reused by every solve
+  DevEvent poll[2];
+  DevEvent tev[3];  // setup / PDHG timing brackets, reused by every solve
   ~LargeSolver() {
-    for (Buf* b : {&ints, &dbls, &st})
-      if (b->p) (void)hipFree(b->p);
-    if (pinned_status) (void)hipHostFree(pinned_status);
-    for (hipEvent_t e : poll)
-      if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : tev)
-      if (e) (void)hipEventDestroy(e);
     if (cap) (void)hipStreamDestroy(cap);
   }
 };
@@ -763,12 +741,10 @@ hipError_t large_solve(LargeSolver* ls, const Batch& b, int k, const int64_t* d,
                o_part = dput((size_t)nparts * kPart);
   LG_TRY(ls->dbls.ensure(sizeof(double) * doff));
   LG_TRY(ls->st.ensure(sizeof(LgState)));
-  if (!ls->pinned_status) LG_TRY(hipHostMalloc(reinterpret_cast<void**>(&ls->pinned_status), 2 * sizeof(int32_t)));
+  LG_TRY(ls->pinned_status.ensure(2 * sizeof(int32_t)));
   if (!ls->cap) LG_TRY(hipStreamCreateWithFlags(&ls->cap, hipStreamNonBlocking));
-  for (hipEvent_t& e : ls->poll)
-    if (!e) LG_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  for (hipEvent_t& e : ls->tev)
-    if (!e) LG_TRY(hipEventCreate(&e));
+  for (DevEvent& e : ls->poll) LG_TRY(e.ensure(hipEventDisableTiming));
+  for (DevEvent& e : ls->tev) LG_TRY(e.ensure());
   hipStream_t cap = ls->cap;
   double* db = ls->dbls.as<double>();
 
@@ -859,7 +835,7 @@ hipError_t large_solve(LargeSolver* ls, const Batch& b, int k, const int64_t* d,
   constexpr int kPoll = 4;
   const int periods = (o.max_iters + a.chk - 1) / a.chk;
   hipError_t ge = hipSuccess;
-  int32_t* ps = ls->pinned_status;
+  int32_t* ps = ls->pinned_status.as<int32_t>();
   ps[0] = ps[1] = -1;
   int pending = -1;  // slot of the outstanding poll
   for (int r = 0; r < periods && ge == hipSuccess; ++r) {

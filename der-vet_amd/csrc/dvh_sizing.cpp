@@ -23,12 +23,8 @@ struct SizingBuf : DevBuf {
 struct SizingState {
   SizingBuf series, cases, lps, starts, desc, indptr, indices, data, c, c0, q, l, u, x, y, stats, istats, sizes, first,
       count;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // whole call; the phase being timed
+  DevEvent ev[4];  // whole call; the phase being timed
   double ms = 0.0, out3[3] = {0.0, 0.0, 0.0};
-  ~SizingState() {
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
 };
 
 void sizing_destroy(SizingState* s) { delete s; }
@@ -40,30 +36,12 @@ namespace {
 using dvh::HandleView;
 using dvh::SizingState;
 
-int fail(const HandleView& v, int code, const std::string& msg) {
-  *v.err = msg;
-  return code;
-}
-
-#define SZ_HIP(v, call)                                                                  \
-  do {                                                                                   \
-    hipError_t e_ = (call);                                                              \
-    if (e_ != hipSuccess) return fail(v, DVH_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
 // The handle's sizing state, created on first use (on the handle's device).
 int state(const HandleView& v, SizingState** out) {
-  SZ_HIP(v, hipSetDevice(v.device));
-  if (!*v.sizing) {
-    SizingState* s = new SizingState();
-    for (auto& e : s->ev)
-      if (hipEventCreate(&e) != hipSuccess) {
-        dvh::sizing_destroy(s);
-        return fail(v, DVH_ERR_HIP, "hipEventCreate failed");
-      }
-    *v.sizing = s;
-  }
+  DVH_VIEW_HIP(v, hipSetDevice(v.device));
+  if (!*v.sizing) *v.sizing = new SizingState();
   *out = *v.sizing;
+  for (DevEvent& e : (*out)->ev) DVH_VIEW_HIP(v, e.ensure());
   return DVH_OK;
 }
 
@@ -72,12 +50,13 @@ int state(const HandleView& v, SizingState** out) {
 int upload_series(const HandleView& v, SizingState* st, const dvh_outage_case* cases, int count,
                   const std::vector<int>& steps, std::vector<dvh::OutageCase>& oc) {
   std::vector<double> data = dvh::outage_stage(cases, count, false);
-  SZ_HIP(v, st->series.ensure(sizeof(double) * data.size()));
+  DVH_VIEW_HIP(v, st->series.ensure(sizeof(double) * data.size()));
   oc.resize(count);
   dvh::outage_stage_fill(cases, count, false, data, st->series.as<double>(), oc.data());
   for (int k = 0; k < count; ++k) oc[k].outage_len = steps[k];
-  SZ_HIP(v, hipMemcpyAsync(st->series.p, data.data(), sizeof(double) * data.size(), hipMemcpyHostToDevice, v.stream));
-  SZ_HIP(v, hipStreamSynchronize(v.stream));  // the staging vector ends here
+  DVH_VIEW_HIP(v, hipMemcpyAsync(st->series.p, data.data(), sizeof(double) * data.size(), hipMemcpyHostToDevice,
+                                 v.stream));
+  DVH_VIEW_HIP(v, hipStreamSynchronize(v.stream));  // the staging vector ends here
   return DVH_OK;
 }
 
@@ -94,21 +73,21 @@ int scan(const HandleView& v, SizingState* st, const std::vector<dvh::OutageCase
     sel[i] = oc[list[i]];
     max_n = std::max(max_n, sel[i].n_steps);
   }
-  SZ_HIP(v, st->cases.ensure(sizeof(dvh::OutageCase) * n));
-  SZ_HIP(v, st->first.ensure(sizeof(int32_t) * n));
-  SZ_HIP(v, st->count.ensure(sizeof(int32_t) * n));
+  DVH_VIEW_HIP(v, st->cases.ensure(sizeof(dvh::OutageCase) * n));
+  DVH_VIEW_HIP(v, st->first.ensure(sizeof(int32_t) * n));
+  DVH_VIEW_HIP(v, st->count.ensure(sizeof(int32_t) * n));
   hipStream_t s = v.stream;
-  SZ_HIP(v, hipMemcpyAsync(st->cases.p, sel.data(), sizeof(dvh::OutageCase) * n, hipMemcpyHostToDevice, s));
-  SZ_HIP(v, hipMemcpyAsync(st->first.p, first.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
-  SZ_HIP(v, hipMemsetAsync(st->count.p, 0, sizeof(int32_t) * n, s));
-  SZ_HIP(v, hipEventRecord(st->ev[2], s));
+  DVH_VIEW_HIP(v, hipMemcpyAsync(st->cases.p, sel.data(), sizeof(dvh::OutageCase) * n, hipMemcpyHostToDevice, s));
+  DVH_VIEW_HIP(v, hipMemcpyAsync(st->first.p, first.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
+  DVH_VIEW_HIP(v, hipMemsetAsync(st->count.p, 0, sizeof(int32_t) * n, s));
+  DVH_VIEW_HIP(v, hipEventRecord(st->ev[2], s));
   hipError_t e = dvh::launch_outage_first_uncovered(st->cases.as<dvh::OutageCase>(), n, max_n, st->first.as<int32_t>(),
                                                     st->count.as<int32_t>(), s);
   if (e != hipSuccess) return fail(v, DVH_ERR_HIP, std::string("launch_outage_first_uncovered: ") + hipGetErrorString(e));
-  SZ_HIP(v, hipEventRecord(st->ev[3], s));
-  SZ_HIP(v, hipMemcpyAsync(first.data(), st->first.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
-  SZ_HIP(v, hipMemcpyAsync(nunc.data(), st->count.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
-  SZ_HIP(v, hipStreamSynchronize(s));
+  DVH_VIEW_HIP(v, hipEventRecord(st->ev[3], s));
+  DVH_VIEW_HIP(v, hipMemcpyAsync(first.data(), st->first.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
+  DVH_VIEW_HIP(v, hipMemcpyAsync(nunc.data(), st->count.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
+  DVH_VIEW_HIP(v, hipStreamSynchronize(s));
   float ms = 0.0f;
   if (hipEventElapsedTime(&ms, st->ev[2], st->ev[3]) == hipSuccess) st->out3[1] += ms;
   for (int i = 0; i < n; ++i)
@@ -163,30 +142,30 @@ int build_batch(const HandleView& v, SizingState* st, const std::vector<dvh::Siz
     tm += d[1];
   }
   const size_t D = sizeof(double), I = sizeof(int32_t);
-  SZ_HIP(v, st->desc.ensure(desc.size() * sizeof(int64_t)));
-  SZ_HIP(v, st->lps.ensure(sizeof(dvh::SizingLP) * n));
-  SZ_HIP(v, st->indptr.ensure(I * tr));
-  SZ_HIP(v, st->indices.ensure(I * tz));
-  SZ_HIP(v, st->data.ensure(D * tz));
-  SZ_HIP(v, st->c.ensure(D * tn));
-  SZ_HIP(v, st->l.ensure(D * tn));
-  SZ_HIP(v, st->u.ensure(D * tn));
-  SZ_HIP(v, st->x.ensure(D * tn));
-  SZ_HIP(v, st->q.ensure(D * tm));
-  SZ_HIP(v, st->y.ensure(D * tm));
-  SZ_HIP(v, st->c0.ensure(D * n));
-  SZ_HIP(v, st->stats.ensure(D * 4 * n));
-  SZ_HIP(v, st->istats.ensure(I * 2 * n));
-  SZ_HIP(v, st->sizes.ensure(D * 4 * n));
+  DVH_VIEW_HIP(v, st->desc.ensure(desc.size() * sizeof(int64_t)));
+  DVH_VIEW_HIP(v, st->lps.ensure(sizeof(dvh::SizingLP) * n));
+  DVH_VIEW_HIP(v, st->indptr.ensure(I * tr));
+  DVH_VIEW_HIP(v, st->indices.ensure(I * tz));
+  DVH_VIEW_HIP(v, st->data.ensure(D * tz));
+  DVH_VIEW_HIP(v, st->c.ensure(D * tn));
+  DVH_VIEW_HIP(v, st->l.ensure(D * tn));
+  DVH_VIEW_HIP(v, st->u.ensure(D * tn));
+  DVH_VIEW_HIP(v, st->x.ensure(D * tn));
+  DVH_VIEW_HIP(v, st->q.ensure(D * tm));
+  DVH_VIEW_HIP(v, st->y.ensure(D * tm));
+  DVH_VIEW_HIP(v, st->c0.ensure(D * n));
+  DVH_VIEW_HIP(v, st->stats.ensure(D * 4 * n));
+  DVH_VIEW_HIP(v, st->istats.ensure(I * 2 * n));
+  DVH_VIEW_HIP(v, st->sizes.ensure(D * 4 * n));
   hipStream_t s = v.stream;
-  SZ_HIP(v, hipMemcpyAsync(st->desc.p, desc.data(), desc.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
-  SZ_HIP(v, hipMemcpyAsync(st->lps.p, lps.data(), sizeof(dvh::SizingLP) * n, hipMemcpyHostToDevice, s));
+  DVH_VIEW_HIP(v, hipMemcpyAsync(st->desc.p, desc.data(), desc.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
+  DVH_VIEW_HIP(v, hipMemcpyAsync(st->lps.p, lps.data(), sizeof(dvh::SizingLP) * n, hipMemcpyHostToDevice, s));
   hipError_t e = dvh::launch_build_sizing(st->lps.as<dvh::SizingLP>(), n, st->desc.as<int64_t>(),
                                           st->indptr.as<int32_t>(), st->indices.as<int32_t>(), st->data.as<double>(),
                                           st->c.as<double>(), st->c0.as<double>(), st->q.as<double>(),
                                           st->l.as<double>(), st->u.as<double>(), s);
   if (e != hipSuccess) return fail(v, DVH_ERR_HIP, std::string("launch_build_sizing: ") + hipGetErrorString(e));
-  SZ_HIP(v, hipStreamSynchronize(s));  // desc and lps are the caller's vectors
+  DVH_VIEW_HIP(v, hipStreamSynchronize(s));  // desc and lps are the caller's vectors
   bt = dvh_packed{n, 0, tn, tm, tz, tr, st->desc.as<int64_t>(), st->indptr.as<int32_t>(), st->indices.as<int32_t>(),
                   st->data.as<double>(), st->c.as<double>(), st->c0.as<double>(), st->q.as<double>(),
                   st->l.as<double>(), st->u.as<double>(), st->x.as<double>(), st->y.as<double>(),
@@ -200,7 +179,7 @@ int upload_starts(const HandleView& v, SizingState* st, const std::vector<std::v
   const int count = (int)S.size();
   size_t total = 0;
   for (int k = 0; k < count; ++k) total += (size_t)cap[k];
-  SZ_HIP(v, st->starts.ensure(sizeof(int32_t) * total));
+  DVH_VIEW_HIP(v, st->starts.ensure(sizeof(int32_t) * total));
   std::vector<int32_t> flat(total, 0);
   region.assign(count, nullptr);
   size_t off = 0;
@@ -209,8 +188,8 @@ int upload_starts(const HandleView& v, SizingState* st, const std::vector<std::v
     region[k] = st->starts.as<int32_t>() + off;
     off += (size_t)cap[k];
   }
-  SZ_HIP(v, hipMemcpyAsync(st->starts.p, flat.data(), sizeof(int32_t) * total, hipMemcpyHostToDevice, v.stream));
-  SZ_HIP(v, hipStreamSynchronize(v.stream));
+  DVH_VIEW_HIP(v, hipMemcpyAsync(st->starts.p, flat.data(), sizeof(int32_t) * total, hipMemcpyHostToDevice, v.stream));
+  DVH_VIEW_HIP(v, hipStreamSynchronize(v.stream));
   return DVH_OK;
 }
 
@@ -290,16 +269,18 @@ int dvh_sizing_windows(dvh_handle* h, const dvh_outage_case* cases, const dvh_si
   std::vector<double> stats(4 * (size_t)count);
   std::vector<int32_t> ist(2 * (size_t)count);
   hipStream_t s = v.stream;
-  SZ_HIP(v, hipMemcpyAsync(stats.data(), st->stats.p, sizeof(double) * stats.size(), hipMemcpyDeviceToHost, s));
-  SZ_HIP(v, hipMemcpyAsync(ist.data(), st->istats.p, sizeof(int32_t) * ist.size(), hipMemcpyDeviceToHost, s));
+  DVH_VIEW_HIP(v, hipMemcpyAsync(stats.data(), st->stats.p, sizeof(double) * stats.size(), hipMemcpyDeviceToHost, s));
+  DVH_VIEW_HIP(v, hipMemcpyAsync(ist.data(), st->istats.p, sizeof(int32_t) * ist.size(), hipMemcpyDeviceToHost, s));
   for (int k = 0; k < count; ++k) {
     const int64_t* d = &desc[8 * (size_t)k];
     if (out[k].x)
-      SZ_HIP(v, hipMemcpyAsync(out[k].x, st->x.as<double>() + d[6], sizeof(double) * d[0], hipMemcpyDeviceToHost, s));
+      DVH_VIEW_HIP(v, hipMemcpyAsync(out[k].x, st->x.as<double>() + d[6], sizeof(double) * d[0], hipMemcpyDeviceToHost,
+                                     s));
     if (out[k].y)
-      SZ_HIP(v, hipMemcpyAsync(out[k].y, st->y.as<double>() + d[7], sizeof(double) * d[1], hipMemcpyDeviceToHost, s));
+      DVH_VIEW_HIP(v, hipMemcpyAsync(out[k].y, st->y.as<double>() + d[7], sizeof(double) * d[1], hipMemcpyDeviceToHost,
+                                     s));
   }
-  SZ_HIP(v, hipStreamSynchronize(s));
+  DVH_VIEW_HIP(v, hipStreamSynchronize(s));
   for (int k = 0; k < count; ++k) {
     dvh_result& r = out[k];
     r.obj = stats[4 * k];
@@ -324,7 +305,7 @@ int dvh_size_reliability(dvh_handle* h, const dvh_outage_case* cases, const dvh_
   if (int rc = state(v, &st)) return rc;
   st->ms = st->out3[0] = st->out3[1] = st->out3[2] = 0.0;
   hipStream_t s = v.stream;
-  SZ_HIP(v, hipEventRecord(st->ev[0], s));
+  DVH_VIEW_HIP(v, hipEventRecord(st->ev[0], s));
 
   // ---- seeds: the first n_seed starts of a stable descending sort of the rolling requirement
   std::vector<int> L(count), cap(count);
@@ -398,16 +379,16 @@ int dvh_size_reliability(dvh_handle* h, const dvh_outage_case* cases, const dvh_
     }
     std::vector<int64_t> desc;
     dvh_packed bt;
-    SZ_HIP(v, hipEventRecord(st->ev[2], s));
+    DVH_VIEW_HIP(v, hipEventRecord(st->ev[2], s));
     if (int rc = build_batch(v, st, lps, desc, bt)) return rc;
     if (int rc = dvh_solve_packed_device(h, &bt, nullptr)) return rc;
     hipError_t e = dvh::launch_gather_sizes(st->desc.as<int64_t>(), st->x.as<double>(), st->istats.as<int32_t>(), na,
                                             st->sizes.as<double>(), s);
     if (e != hipSuccess) return fail(v, DVH_ERR_HIP, std::string("launch_gather_sizes: ") + hipGetErrorString(e));
-    SZ_HIP(v, hipEventRecord(st->ev[3], s));
+    DVH_VIEW_HIP(v, hipEventRecord(st->ev[3], s));
     std::vector<double> sizes(4 * (size_t)na);
-    SZ_HIP(v, hipMemcpyAsync(sizes.data(), st->sizes.p, sizeof(double) * sizes.size(), hipMemcpyDeviceToHost, s));
-    SZ_HIP(v, hipStreamSynchronize(s));
+    DVH_VIEW_HIP(v, hipMemcpyAsync(sizes.data(), st->sizes.p, sizeof(double) * sizes.size(), hipMemcpyDeviceToHost, s));
+    DVH_VIEW_HIP(v, hipStreamSynchronize(s));
     float ms = 0.0f;
     if (hipEventElapsedTime(&ms, st->ev[2], st->ev[3]) == hipSuccess) st->out3[0] += ms;
     // (2), (3) candidates and their limits
@@ -470,8 +451,8 @@ int dvh_size_reliability(dvh_handle* h, const dvh_outage_case* cases, const dvh_
     out[k].n_starts = (int32_t)S[k].size();
     if (out[k].starts) std::copy(S[k].begin(), S[k].end(), out[k].starts);
   }
-  SZ_HIP(v, hipEventRecord(st->ev[1], s));
-  SZ_HIP(v, hipStreamSynchronize(s));
+  DVH_VIEW_HIP(v, hipEventRecord(st->ev[1], s));
+  DVH_VIEW_HIP(v, hipStreamSynchronize(s));
   float ms = 0.0f;
   if (hipEventElapsedTime(&ms, st->ev[0], st->ev[1]) == hipSuccess) st->ms = ms;
   return DVH_OK;

@@ -69,9 +69,8 @@ int certify_pass(dvh_handle* h, const dvh_packed* bt, const std::vector<int64_t>
   DVH_HIP(h, h->c_sig.ensure(D * (size_t)sm));
   DVH_HIP(h, h->c_gy.ensure(D * (size_t)sm));
   DVH_HIP(h, h->c_counts.ensure(I * 5));
-  if (!h->cert_host) DVH_HIP(h, hipHostMalloc((void**)&h->cert_host, I * 5, hipHostMallocDefault));
-  for (auto& e : h->cert_ev)
-    if (!e) DVH_HIP(h, hipEventCreate(&e));
+  DVH_HIP(h, h->cert_host.ensure(I * 5));
+  for (DevEvent& e : h->cert_ev) DVH_HIP(h, e.ensure());
   dvh::CertWork cw{h->c_tptr.as<int32_t>(), h->c_tind.as<int32_t>(), h->c_tval.as<double>(), h->c_tau.as<double>(),
                    h->c_gx.as<double>(), h->c_sig.as<double>(), h->c_gy.as<double>(), h->c_counts.as<int32_t>(),
                    bn, bm, bz};
@@ -80,7 +79,7 @@ int certify_pass(dvh_handle* h, const dvh_packed* bt, const std::vector<int64_t>
   DVH_HIP(h, hipEventRecord(h->cert_ev[0], s));
   DVH_HIP(h, dvh::launch_certify(make_batch(*bt), cw, count, mn, mm, cap, gate, s));
   DVH_HIP(h, hipEventRecord(h->cert_ev[1], s));
-  DVH_HIP(h, hipMemcpyAsync(h->cert_host, h->c_counts.p, I * 5, hipMemcpyDeviceToHost, s));
+  DVH_HIP(h, hipMemcpyAsync(h->cert_host.p, h->c_counts.p, I * 5, hipMemcpyDeviceToHost, s));
   h->cert_pending = true;
   return DVH_OK;
 }
@@ -195,25 +194,17 @@ int make_work(dvh_handle* h, const BatchPlan& p, dvh::Work& w) {
                 h->w_fc.as<float>(), h->w_fr.as<float>(), h->w_queue.as<int32_t>(), h->band_slots};
   DVH_HIP(h, h->d_list.ensure(I * 5 * (size_t)wc));  // the cascade's five device lists (dvh_route.hip)
   DVH_HIP(h, h->d_route.ensure(I * 8 * 5));
-  if (!h->route_host) DVH_HIP(h, hipHostMalloc((void**)&h->route_host, I * 8 * 5, hipHostMallocDefault));
+  DVH_HIP(h, h->route_host.ensure(I * 8 * 5));
   return DVH_OK;
 }
 
 // The next set of per-chunk timing events of the handle's pool (grown on demand).
-int next_chunk_events(dvh_handle* h, const hipEvent_t*& out) {
-  if (h->st.chunk_used == h->chunk_events.size()) {
-    std::array<hipEvent_t, 3> ce{nullptr, nullptr, nullptr};
-    for (hipEvent_t& e : ce) {
-      const hipError_t r = hipEventCreate(&e);
-      if (r != hipSuccess) {
-        for (hipEvent_t x : ce)
-          if (x) hipEventDestroy(x);
-        return hip_fail(h, r, "hipEventCreate");
-      }
-    }
-    h->chunk_events.push_back(ce);
-  }
-  out = h->chunk_events[h->st.chunk_used++].data();
+int next_chunk_events(dvh_handle* h, const DevEvent*& out) {
+  if (h->st.chunk_used == h->chunk_events.size()) h->chunk_events.emplace_back();
+  std::array<DevEvent, 3>& ce = h->chunk_events[h->st.chunk_used];
+  for (DevEvent& e : ce) DVH_HIP(h, e.ensure());  // (a set whose creation failed half-way is completed here)
+  ++h->st.chunk_used;
+  out = ce.data();
   return DVH_OK;
 }
 
@@ -310,7 +301,7 @@ int solve_packed(dvh_handle* h, const dvh_packed* bt, const std::vector<int64_t>
   std::vector<char> med_done(count, 0);  // solved (or reported infeasible) by the medium tier
   for (const ChunkPlan& c : plan.chunks) {
     if (c.nsmall == 0 && c.med.empty()) continue;
-    const hipEvent_t* ce = nullptr;
+    const DevEvent* ce = nullptr;
     if (int rc = next_chunk_events(h, ce)) return rc;
     DVH_HIP(h, hipEventRecord(ce[0], s));
     // (the device cascade sets up only what the band kernel refuses, inside device_cascade)
@@ -326,9 +317,9 @@ int solve_packed(dvh_handle* h, const dvh_packed* bt, const std::vector<int64_t>
   // windows above the on-chip limits that the medium tier did not take: one at a time, the whole GPU each
   for (int k : plan.large) {
     if (med_done[k]) continue;
-    if (!h->large) h->large = dvh::large_create();
+    if (!h->large) h->large.reset(dvh::large_create());
     std::string msg;
-    hipError_t e = dvh::large_solve(h->large, b, k, &desc[8 * (size_t)k], o, h->d_hinv.as<double>(), s, &msg,
+    hipError_t e = dvh::large_solve(h->large.get(), b, k, &desc[8 * (size_t)k], o, h->d_hinv.as<double>(), s, &msg,
                                     &h->st.large_ms[0], &h->st.large_ms[1]);
     if (e != hipSuccess) return fail(h, DVH_ERR_HIP, "window " + std::to_string(k) + ": " + msg);
     ++h->st.n_large;
@@ -357,7 +348,7 @@ int finish_timing(dvh_handle* h, hipStream_t s) {
   st.timing[0] = st.timing[1] = st.timing[2] = 0;
   if (hipEventElapsedTime(&t, h->ev[0], h->ev[3]) == hipSuccess) st.timing[0] = t;
   if (h->cert_pending) {  // the certificate pass's counters and time (copied behind it on the stream)
-    for (int i = 0; i < 5; ++i) st.cert[i] = h->cert_host[i];
+    for (int i = 0; i < 5; ++i) st.cert[i] = h->cert_host.as<int32_t>()[i];
     if (hipEventElapsedTime(&t, h->cert_ev[0], h->cert_ev[1]) == hipSuccess) st.cert_ms = t;
     h->cert_pending = false;
   }

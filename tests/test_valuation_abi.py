@@ -45,6 +45,11 @@ N = 3 * T + J
 @pytest.fixture(scope="module")
 def world(gpu_solver):
     """A valid bill call and a valid valuation call; every case below breaks one argument of a copy."""
+    return make_world(gpu_solver)
+
+
+def make_world(solver):
+    """(solver, batch, tensors) of the two calls (tests/test_gpu_handle_lifetime.py runs them on handles of its own)."""
     import torch
     from dervet_hip.packed import PackedBatch
     z = np.zeros
@@ -61,7 +66,7 @@ def world(gpu_solver):
              idx=torch.tensor([0, 1, 2], dtype=torch.int32, device="cuda:0"),
              year=torch.zeros(3, dtype=torch.int32, device="cuda:0"), capex=torch.ones(2, **f64))
     torch.cuda.synchronize()
-    return gpu_solver, pb, t
+    return solver, pb, t
 
 
 def bill_call(world, edit=None, first=0, bills=True, bad=True):
