@@ -208,7 +208,9 @@ def interconnect_windows():
     return out
 
 
-CHAIN = ((1400, 0), (1400, 1))  # 3 T + J > 4096: two segments; J = 1: the demand period spans both
+# 3 T + J > 4096: the chain team.  J = 0: two segments.  J = 1: the demand period, steps [350, 1050), gets a segment of
+# its own (the plan's run_cut), so three segments and no shared column; CHAIN_PLAN below holds the windows that share
+CHAIN = ((1400, 0), (1400, 1))
 
 
 @functools.lru_cache(maxsize=None)
@@ -218,6 +220,78 @@ def chain_windows():
         base = planted_lp.from_window(battery_window(T, J, span=True))
         out[f"chainT{T}J{J}"] = (base, planted_lp.planted_window(base, 1))
     return out
+
+
+# ---- the chain team's plan (csrc/dvh_chain.hip chain_plan_kernel, restated in tests/chain_plan_ref.py): one window per
+# branch of the plan and of what the team kernel does with it.
+# name -> (T, J, tau id per step (-1: no demand row), the plan's segment starts or None where the plan refuses the
+# window, the (slot, other sharer) pairs of every segment, what the case reaches).  The plans are derived by hand from
+# the kernel source; tests/test_chain_plan_ref.py holds the restatement to them.  No GPU test solves these windows
+# yet, and none may solve s65_J2 before the plan refuses it: its 128 pairs are one more than a segment's poll lists
+# hold (tests/chain_plan_ref.py).
+
+
+def _pieces(T, *pieces):
+    """tau ids from (start, id) pieces, each running to the next piece's start; id "tN" = t % N."""
+    t = np.arange(T)
+    out = np.full(T, -1, np.int64)
+    for (a, j), (e, _) in zip(pieces, pieces[1:] + ((T, None),)):
+        out[a:e] = t[a:e] % int(j[1:]) if isinstance(j, str) else j
+    return out
+
+
+def _peak(T, other):
+    """dt = 0.25: hours 12-17 of each day (steps 48 .. 71 of 96) are column 0, the rest `other`."""
+    hour = (np.arange(T) % 96) // 4
+    return np.where((hour >= 12) & (hour < 18), 0, other)
+
+
+def _full(T):
+    return tuple(range(0, T, 768)) + (T,)
+
+
+CHAIN_PLAN = {
+    "min_J0": (1366, 0, _pieces(1366, (0, -1)), (0, 768, 1366), 0, "smallest chain window: 3 T > 4096"),
+    "route_J2": (1365, 2, _pieces(1365, (0, "t2")), (0, 768, 1365), 2, "n = 4097: the chain, next to its on-chip twin"),
+    "all_J1": (1400, 1, _pieces(1400, (0, 0)), (0, 768, 1400), 1, "one shared column"),
+    "all_J2": (1400, 2, _pieces(1400, (0, "t2")), (0, 768, 1400), 2, "nsl > 1"),
+    "all_J4": (1400, 4, _pieces(1400, (0, "t4")), (0, 768, 1400), 4, "all four slots shared"),
+    "five_J5": (1400, 5, _pieces(1400, (0, "t5")), None, None, "refused: 4-step segments until kPMax"),
+    "full_J1": (1536, 1, _pieces(1536, (0, 0)), (0, 768, 1536), 1, "lane 767 is the last step of both segments"),
+    "tail1_J1": (1537, 1, _pieces(1537, (0, 0)), (0, 768, 1536, 1537), 2, "one-step last segment sharing a column"),
+    "tail64_J1": (1600, 1, _pieces(1600, (0, 0)), (0, 768, 1536, 1600), 2, "last segment of 64 steps: wl = 0"),
+    "tail65_J1": (1601, 1, _pieces(1601, (0, 0)), (0, 768, 1536, 1601), 2, "last segment of 65 steps: wl = 1"),
+    "mid1_J3": (2305, 3, _pieces(2305, (0, -1), (767, 0), (1535, 1), (1536, 2), (2304, 1)),
+                (0, 767, 1535, 1536, 2304, 2305), (0, 0, 2, 2, 2),
+                "one-step middle and last segments; segment 3 holds column 1 in a free slot"),
+    "free_J2": (2304, 2, _pieces(2304, (0, 1), (768, 0), (1536, 1)), (0, 768, 1536, 2304), 2,
+                "free-slot sharer with zero partials"),
+    "nofree_J5": (2304, 5, _pieces(2304, (0, 4), (768, "t4"), (1536, 4)), None, None, "refused: no free slot"),
+    "qh_peak_J2": (2976, 2, _peak(2976, 1), (0, 744, 1512, 2280, 2976), 6, "two-period tariff; run_cut starts"),
+    "qh_peak_J1": (2976, 1, _peak(2976, -1), (0, 744, 1512, 2280, 2976), 3, "shared column, steps without a row"),
+    "s64_J1": (49152, 1, _pieces(49152, (0, 0)), _full(49152), 63, "DPP tau_total with all 64 lanes; long set-up"),
+    "s65_J1": (49920, 1, _pieces(49920, (0, 0)), _full(49920), 64, "sequential tau_total branch"),
+    "s64_J2": (49152, 2, _pieces(49152, (0, "t2")), _full(49152), 126, "K list at 254 of 256 entries"),
+    "s65_J2": (49920, 2, _pieces(49920, (0, "t2")), _full(49920), 128, "one pair past the poll lists, and planned"),
+}
+CHAIN_PLAN_LONG = tuple(n for n in CHAIN_PLAN if n.startswith("s6"))  # the 49k windows: the planted twin only
+CHAIN_PLAN_OVERFLOW = ("s65_J2",)  # planned with more pairs than the team kernel's poll lists hold
+ROUTE_TWIN = (1365, 1)  # route_J2's on-chip twin: n = 4096 stays with the on-chip kernels
+
+
+@functools.lru_cache(maxsize=None)
+def chain_plan_window(name, seed=5):
+    """(realistic oracle dict, planted oracle dict) of a CHAIN_PLAN case."""
+    T, J, tau = CHAIN_PLAN[name][:3]
+    masks = np.array([tau == j for j in range(J)], bool).reshape(J, T) if J else None
+    base = planted_lp.from_window(band_cases.window(T, J, seed, masks=masks)[0])
+    return base, planted_lp.planted_window(base, 1)
+
+
+@functools.lru_cache(maxsize=None)
+def route_twin():
+    T, J = ROUTE_TWIN
+    return planted_lp.from_window(band_cases.window(T, J, 5, masks=np.ones((J, T), bool))[0])
 
 
 def all_window_cases():
