@@ -197,6 +197,13 @@ int dvh_last_certify(const dvh_handle* h, int32_t* out5) {
   return DVH_OK;
 }
 
+int dvh_last_certify_early(const dvh_handle* h, int32_t* out2) {
+  if (!h || !out2) return DVH_ERR_ARG;
+  out2[0] = h->st.cert_early[0];
+  out2[1] = h->st.cert_early[1];
+  return DVH_OK;
+}
+
 int dvh_last_certify_ms(const dvh_handle* h, double* ms) {
   if (!h || !ms) return DVH_ERR_ARG;
   *ms = h->st.cert_ms;

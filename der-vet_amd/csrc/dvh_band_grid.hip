@@ -70,6 +70,20 @@ __device__ __noinline__ ColKktX grid_col_kkt(double kt, double cj, double loj, d
   r.rdx = fabs(rd) * fabs(xj * (double)fd);
   return r;
 }
+// CERT: the Farkas terms of one column from kt = (K~'y~)_j and its scaled bounds: the bound term of the margin (finite
+// bound on kt's side) or the violation |kt| / Dc_j (infinite bound).  Out of line for the same reason.
+struct ColFarkas {
+  double bt, viol;
+};
+__device__ __noinline__ ColFarkas grid_col_farkas(double kt, double loj, double hij, const double* dc) {
+  ColFarkas f = {0.0, 0.0};
+  if (kt > 0.0) {
+    if (hij < INFINITY) f.bt = hij * kt; else f.viol = kt / *dc;
+  } else if (kt < 0.0) {
+    if (loj > -INFINITY) f.bt = loj * kt; else f.viol = -kt / *dc;
+  }
+  return f;
+}
 struct RowKkt {
   double rp2, y2;
 };
@@ -80,9 +94,39 @@ __device__ __noinline__ RowKkt grid_row_kkt(double kv, double qi, double yi, flo
   return {r * r, (yi * dr) * (yi * dr)};
 }
 
+// Three sums and one maximum over the workgroup (CERT), fixed order: wave reductions, one barrier, then every lane
+// combines the NW partials in wave order -- identical in all lanes.  red[0 .. 4 NW) must be free (a barrier since its
+// last read) and is not reused before another barrier has passed.
 template <int B>
+__device__ __forceinline__ void grid_farkas_reduce(double (&s)[3], double mx, double& mx_out, double* red) {
+  constexpr int NW = B / kWave;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+  for (int u = 0; u < 3; ++u) s[u] = wave_sum_dpp(s[u]);
+  mx = wave_max(mx);
+  if (lane == 0) {
+#pragma unroll
+    for (int u = 0; u < 3; ++u) red[wid * 4 + u] = s[u];
+    red[wid * 4 + 3] = mx;
+  }
+  lds_barrier();
+  double t[3] = {0.0, 0.0, 0.0}, m = 0.0;
+  for (int w = 0; w < NW; ++w) {
+#pragma unroll
+    for (int u = 0; u < 3; ++u) t[u] += red[w * 4 + u];
+    m = fmax(m, red[w * 4 + 3]);
+  }
+#pragma unroll
+  for (int u = 0; u < 3; ++u) s[u] = uniform(t[u]);
+  mx_out = uniform(m);
+}
+
+// CERT (dvh_options.certify = 2): the Farkas test of the scaled dual of T(z_k) at every KKT check, before the
+// termination test, as pdhg_kernel's (dvh_kernels.hip); early = {windows certified here, their largest iteration
+// count}.  CERT = false compiles none of it.
+template <int B, bool CERT>
 __device__ __forceinline__ void grid_window(const Batch& b, const Work& w, const Chunk& ch, const Opts& o, const int k_in,
-                                            const int tid) {
+                                            const int tid, int32_t* early) {
   const int k = __builtin_amdgcn_readfirstlane(k_in);
   // only what the earlier passes refused (the launch follows them on the same list, before the list is formed again)
   if (__builtin_amdgcn_readfirstlane(b.istats[2 * k]) != kNeedsEll) return;
@@ -827,6 +871,48 @@ __device__ __forceinline__ void grid_window(const Batch& b, const Work& w, const
 #pragma unroll
       for (int u = 0; u < 4; ++u) acc[u] = acc4[u];
     }
+    if constexpr (CERT) {
+      if (__builtin_expect(kkt, false)) {
+        // The Farkas terms in a pass of their own behind the check's reduction, whose sums are scalar by now (the
+        // images still hold T(z_k)): fk = sum of the bound terms of K~'y~, of their absolute values, sum |q~_i y~_i|;
+        // fv = the largest |(K'v)_j| on the side of an infinite bound.  (Uniform: every wave takes the reduction and
+        // leaves at the same barrier.)
+        double fk[3] = {0.0, 0.0, 0.0}, fv = 0.0;
+        auto col_farkas = [&](int j, double kt, double loj, double hij) {
+          const ColFarkas f = grid_col_farkas(kt, loj, hij, dcv + opaque(j));
+          fk[0] += f.bt;
+          fk[1] += fabs(f.bt);
+          fv = fmax(fv, f.viol);
+        };
+        {
+          double yp[NR], kt[NC];
+  #pragma unroll
+          for (int r = 0; r < NR; ++r) yp[r] = ypi(r);
+          ktr(yp, YS[tid], kt);
+          if (val) {
+            col_farkas(t, kt[0], 0.0, hi[0]);
+            col_farkas(T + t, kt[1], 0.0, hi[1]);
+            col_farkas(2 * T + t, kt[2], loe, hi[2]);
+            if (PV) col_farkas(CP + t, kt[3], 0.0, ro(1));
+          }
+  #pragma unroll
+          for (int r = 0; r < NR; ++r)
+            if (row_of(r) >= 0) fk[2] += fabs(rhs(r) * yp[r]);
+        }
+        if (wid == 0 && J > 0) {
+          const double ktt = tau_kt();
+          if (tlane) col_farkas(3 * T + lane, ktt, -INFINITY, INFINITY);
+        }
+        if (ilane) fk[2] += fabs(sp[3] * sp[2]);
+        double viol;
+        lds_barrier();  // (red: the check's partials have been read by every wave)
+        grid_farkas_reduce<B>(fk, fv, viol, red);
+        if (farkas_passes(acc[7] - fk[0], viol, fk[2] + fk[1])) {
+          status = kPrimalInfeasible;
+          break;
+        }
+      }
+    }
     const double r = uniform(sqrt(pw * acc[0] + acc[2] / pw));
     if (kkt) {
       const double pobj = uniform(acc[6] + c0), dobj = uniform(acc[7] + acc[8] + c0);
@@ -880,6 +966,87 @@ __device__ __forceinline__ void grid_window(const Batch& b, const Work& w, const
     // (a restart check that neither restarts nor checks KKT rewrote no shared value: the next iteration reads what the
     // check iteration wrote before its barriers, and `red` is next written two barriers later -- no barrier here)
   }
+  if constexpr (CERT) {
+    if (__builtin_expect(status == kPrimalInfeasible, false)) {
+      // certified at the last check: YS / TP still hold the images of y~ of T(z_k).  y = v / ||v||_inf with v = Dr y~;
+      // the margin and the violation of that y on the unscaled window (double factors, the window's own q, l, u), as
+      // the after-pass reports them; x is the last checked candidate, written as below, and means nothing
+      if (val) {
+#pragma unroll
+        for (int v = 0; v < NC; ++v) {
+          if (v == 3 && !PV) continue;
+          const int j = col(v);
+          xo_g[j] = unscale_x(xpi(v), dcv[j], lraw[j], uraw[j]);
+        }
+      }
+      if (tlane) xo_g[3 * T + lane] = unscale_x(sp[5], dcv[3 * T + lane], lraw[3 * T + lane], uraw[3 * T + lane]);
+      double yp[NR], vr[NR];
+      double nv = 0.0;
+#pragma unroll
+      for (int r = 0; r < NR; ++r) {
+        yp[r] = ypi(r);
+        const int i = row_of(r);
+        vr[r] = i >= 0 ? yp[r] * drv[i] : 0.0;
+        nv = fmax(nv, fabs(vr[r]));
+      }
+      const double v0 = ilane ? sp[2] * drv[0] : 0.0;
+      nv = fmax(nv, fabs(v0));
+      double z3[3] = {0.0, 0.0, 0.0}, nrm;
+      lds_barrier();  // (red: the check's reduction has been read by every wave)
+      grid_farkas_reduce<B>(z3, nv, nrm, red);
+      double ea[3] = {0.0, 0.0, 0.0};  // q'y, the bound terms of K'y, unused
+      double ev = 0.0;
+#pragma unroll
+      for (int r = 0; r < NR; ++r) {
+        const int i = row_of(r);
+        if (i >= 0) {
+          const double v = vr[r] / nrm;
+          yo_g[i] = v;
+          ea[0] += qraw[i] * v;
+        }
+      }
+      if (ilane) {
+        yo_g[0] = v0 / nrm;
+        ea[0] += qraw[0] * (v0 / nrm);
+      }
+      auto col_exit = [&](int j, double kt) {
+        const double r = kt / nrm / dcv[j];
+        const double lj = lraw[j], uj = uraw[j];
+        if (r > 0.0) {
+          if (uj < INFINITY) ea[1] += uj * r; else ev = fmax(ev, r);
+        } else if (r < 0.0) {
+          if (lj > -INFINITY) ea[1] += lj * r; else ev = fmax(ev, -r);
+        }
+      };
+      {
+        double kt[NC];
+        ktr(yp, YS[tid], kt);
+        if (val) {
+#pragma unroll
+          for (int v = 0; v < NC; ++v)
+            if (v < 3 || PV) col_exit(col(v), kt[v]);
+        }
+      }
+      if (wid == 0 && J > 0) {
+        const double ktt = tau_kt();
+        if (tlane) col_exit(3 * T + lane, ktt);
+      }
+      double viol;
+      lds_barrier();
+      grid_farkas_reduce<B>(ea, ev, viol, red);
+      if (tid == 0) {
+        b.istats[2 * k] = kPrimalInfeasible;
+        b.istats[2 * k + 1] = it;
+        b.stats[4 * k] = INFINITY;
+        b.stats[4 * k + 1] = ea[0] - ea[1];
+        b.stats[4 * k + 2] = viol;
+        b.stats[4 * k + 3] = 0.0;
+        atomicAdd(&early[0], 1);
+        atomicMax(&early[1], it);
+      }
+      return;
+    }
+  }
   // outputs: the last check's T(z_k), unscaled with the exact double factors
   if (val) {
 #pragma unroll
@@ -910,25 +1077,38 @@ struct GridArgs {
   Opts o;
   const int32_t* list;  // global window indices, or null: the chunk
 };
-template <int B>
-__global__ __launch_bounds__(B, 3) void pdhg_band_grid_kernel(const GridArgs args) {
+struct GridArgsCert : GridArgs {
+  int32_t* early;  // the handle's early-certificate counters
+};
+// (CERT = false takes the arguments it always took)
+template <int B, bool CERT = false>
+__global__ __launch_bounds__(B, 3) void pdhg_band_grid_kernel(const std::conditional_t<CERT, GridArgsCert, GridArgs> args) {
   const int i = blockIdx.x;
-  grid_window<B>(args.b, args.w, args.ch, args.o, args.list ? args.list[i] : args.ch.first + i, threadIdx.x);
+  int32_t* early = nullptr;
+  if constexpr (CERT) early = args.early;
+  grid_window<B, CERT>(args.b, args.w, args.ch, args.o, args.list ? args.list[i] : args.ch.first + i, threadIdx.x, early);
 }
 
 }  // namespace
 
 hipError_t launch_pdhg_band_grid(const Batch& b, const Work& w, const Chunk& ch, const Opts& o, hipStream_t s,
-                                 const int32_t* list, int nlist, int* variant_out) {
+                                 const int32_t* list, int nlist, int* variant_out, int32_t* early) {
   constexpr int B = kGridB;
   const size_t lds = grid_lds_bytes(B);
-  auto kern = pdhg_band_grid_kernel<B>;
-  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  const void* kern = early ? (const void*)pdhg_band_grid_kernel<B, true> : (const void*)pdhg_band_grid_kernel<B, false>;
+  hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
   const int count = list ? nlist : ch.count;
   if (count <= 0) return hipSuccess;
   const GridArgs args{b, w, ch, o, list};
-  hipLaunchKernelGGL(kern, dim3(count), dim3(B), lds, s, args);
+  if (early) {
+    GridArgsCert ac;
+    static_cast<GridArgs&>(ac) = args;
+    ac.early = early;
+    hipLaunchKernelGGL((pdhg_band_grid_kernel<B, true>), dim3(count), dim3(B), lds, s, ac);
+  } else {
+    hipLaunchKernelGGL((pdhg_band_grid_kernel<B, false>), dim3(count), dim3(B), lds, s, args);
+  }
   if (variant_out) *variant_out = 9000000 + 200 + B / kWave;
   return hipGetLastError();
 }

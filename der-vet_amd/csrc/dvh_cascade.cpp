@@ -226,7 +226,7 @@ int device_cascade(dvh_handle* h, const dvh::Batch& b, const dvh::Work& w, const
     // the stream: its workgroups leave at once unless their window is still refused (-2), so the route below sees the
     // final statuses and the mode adds no read-back.  (Which of the two forms took the pass's windows is not read
     // back either: the pass reports the interconnection form's variant code.)
-    if (h->kernel_path == 5) DVH_HIP(h, dvh::launch_pdhg_band_grid(b, w, ch, o, s, L[0], cur, &bvar));
+    if (h->kernel_path == 5) DVH_HIP(h, dvh::launch_pdhg_band_grid(b, w, ch, o, s, L[0], cur, &bvar, early_counters(h)));
     DVH_HIP(h, route(1, L[0], cur, -2, 0, 4));
     if (box_ice) DVH_HIP(h, route(2, L[0], cur, -3, 0, 1));
     DVH_HIP(h, readback(1, box_ice ? 2 : 1));
@@ -293,7 +293,7 @@ int device_cascade(dvh_handle* h, const dvh::Batch& b, const dvh::Work& w, const
   if (gn > 0) {
     DVH_HIP(h, dvh::launch_power(b, w, ch, o, gl, gn, s));
     int gv = -1;
-    hipError_t e = dvh::launch_pdhg(b, w, ch, o, gm[0], gm[1], gm[2], s, &gv, gl, gn);
+    hipError_t e = dvh::launch_pdhg(b, w, ch, o, gm[0], gm[1], gm[2], s, &gv, gl, gn, early_counters(h));
     if (e == hipErrorInvalidValue)
       return fail(h, DVH_ERR_UNSUPPORTED, "window too large for the on-chip PDHG kernels (n or m > 4096)");
     if (e != hipSuccess) return hip_fail(h, e, "launch_pdhg");

@@ -13,7 +13,7 @@ constexpr int kNRed = 11;  // values reduced by a termination (KKT) check
 constexpr int kRdx = 10;   // the slot of sum_j |r_d,j| |x_j|, the objective gate's dual-residual term (kkt_done)
 __host__ __device__ constexpr size_t align16(size_t x) { return (x + 15) & ~size_t(15); }
 
-constexpr int kOptimal = 0, kIterLimit = 3, kNumerical = 4;
+constexpr int kOptimal = 0, kPrimalInfeasible = 1, kIterLimit = 3, kNumerical = 4;
 
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
@@ -121,6 +121,28 @@ __device__ __forceinline__ void block_sum(double (&v)[NV], double* red) {
 #pragma unroll
   for (int k = 0; k < NV; ++k) v[k] = red[NW * NV + k];
   __syncthreads();
+}
+
+// Block maximum of a non-negative value (fixed order: wave butterfly, then the waves in order); red must hold NW
+// doubles.  Result identical in all threads; red is free again on return.
+template <int B>
+__device__ __forceinline__ double block_max(double v, double* red) {
+  constexpr int NW = B / kWave;
+  v = wave_max(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double r = red[0];
+  for (int w = 1; w < NW; ++w) r = fmax(r, red[w]);
+  __syncthreads();
+  return r;
+}
+
+// The in-kernel Farkas test's acceptance (dvh_options.certify = 2; pdhg_kernel, pdhg_band_grid_kernel): the constants
+// and meaning of the certificate pass's (dvh_certify.hip cert_passes, tests/certify_ref._passes) -- margin > 0, the
+// violation within PDLP's ray tolerance of it, and the margin above the round-off of the terms it is the difference
+// of.  False for a NaN in any argument.
+__device__ __forceinline__ bool farkas_passes(double margin, double viol, double scale) {
+  return margin > 0.0 && viol <= 1e-8 * margin && margin >= 1e-9 * scale;
 }
 
 // One-barrier variant: per-wave partials in red[wave*NV + k], one __syncthreads, then every lane adds the

@@ -15,6 +15,7 @@ struct SolveStats {
   float large_ms[2] = {0, 0};  // setup, PDHG time of the large windows
   size_t chunk_used = 0;       // the handle's chunk_events the solve recorded
   int32_t cert[5] = {0, 0, 0, 0, 0};  // certificate pass (dvh_last_certify), set by certify_reset / finish_timing
+  int32_t cert_early[2] = {0, 0};     // in-kernel certificates (dvh_last_certify_early), set likewise
   double cert_ms = 0.0;
   double timing[3] = {0, 0, 0};  // whole solve, setup, PDHG (dvh_last_timing), set by finish_timing
   // a solve's start: everything it counts itself
@@ -36,6 +37,8 @@ struct SolveStats {
     warn += p.warn;
     for (int u = 0; u < 4; ++u) cert[u] += p.cert[u];
     cert[4] = std::max(cert[4], p.cert[4]);
+    cert_early[0] += p.cert_early[0];
+    cert_early[1] = std::max(cert_early[1], p.cert_early[1]);
     cert_ms = std::max(cert_ms, p.cert_ms);
     for (int u = 1; u < 3; ++u) timing[u] = std::max(timing[u], p.timing[u]);
   }
@@ -97,7 +100,10 @@ struct dvh_handle : dvh_handle_core {
   DevBuf d_route;                                 // cascade lists' counts / ELL widths (dvh_route.hip)
   // certificate pass (dvh_certify.hip): its workspace (allocated on first use) and the device counters
   DevBuf c_tptr, c_tind, c_tval, c_tau, c_gx, c_sig, c_gy, c_counts;
-  bool cert_pending = false;
+  // certify = 2: {windows certified inside a PDHG kernel, their largest iteration count}, zeroed at a solve's start,
+  // copied to cert_host[5 .. 6] behind the pass
+  DevBuf c_early;
+  bool cert_pending = false, cert_early_pending = false;
   DevBuf v_zwork;  // economic sizing's cut pass (dvh_api_value_sizing.cpp): z of the windows above the LDS size, G * T
   int n_syncs = 0;                                // host waits on the stream in the last solve
   double outage_ms = 0.0;
@@ -124,6 +130,10 @@ inline hipError_t sync_stream(dvh_handle* h, hipStream_t s) {
   ++h->n_syncs;
   return hipStreamSynchronize(s);
 }
+
+// The early-certificate counters for the kernels that test inside the loop, or null below level 2 (the launchers then
+// take the instantiations without the test).
+inline int32_t* early_counters(dvh_handle* h) { return h->opts.certify >= 2 ? h->c_early.as<int32_t>() : nullptr; }
 
 inline int fail(dvh_handle* h, int code, const std::string& msg) {
   if (h) h->err = msg;

@@ -124,8 +124,11 @@ hipError_t launch_setup(const Batch& b, const Work& w, const Chunk& ch, const Op
 // Solve kernel selection is made from the chunk maxima; returns hipErrorInvalidValue when no
 // instantiation covers the sizes (the caller reports DVH_ERR_UNSUPPORTED).
 // Generic (CSR) kernel; list = optional device list of window ids (nlist blocks) instead of the whole chunk.
+// early (device, int32[2]; dvh_options.certify = 2) != null: the instantiations with the in-kernel Farkas test (the
+// certificate block below); early[0] += the windows they certify, early[1] = max(early[1], their iteration counts).
 hipError_t launch_pdhg(const Batch& b, const Work& w, const Chunk& ch, const Opts& o, int max_n, int max_m,
-                       int64_t max_nnz, hipStream_t s, int* variant_out, const int32_t* list, int nlist);
+                       int64_t max_nnz, hipStream_t s, int* variant_out, const int32_t* list, int nlist,
+                       int32_t* early = nullptr);
 // ELL fast-path kernel over the whole chunk, or over the listed windows (wx, wy: ELL widths for K^T and K).
 // Windows that do not fit its shape come back with istats status -1 (kNeedsGeneric) and must be re-run by
 // launch_pdhg.
@@ -291,9 +294,9 @@ hipError_t large_solve(LargeSolver* ls, const Batch& b, int k, const int64_t* d,
 // The band kernel's interconnection form (dvh_band_grid.hip; dvh_set_kernel_path 5): battery windows with POI limit
 // rows, a curtailable-PV column block and / or charge-from-PV rows, one workgroup per listed window.  A workgroup
 // returns at once unless its window's status is -2 (kNeedsEll), so the launch follows the ICE pass over the same
-// list; windows it refuses keep status -2.  variant_out: 9000000 + 200 + waves per window.
+// list; windows it refuses keep status -2.  variant_out: 9000000 + 200 + waves per window.  early: as launch_pdhg's.
 hipError_t launch_pdhg_band_grid(const Batch& b, const Work& w, const Chunk& ch, const Opts& o, hipStream_t s,
-                                 const int32_t* list, int nlist, int* variant_out);
+                                 const int32_t* list, int nlist, int* variant_out, int32_t* early = nullptr);
 
 // Certificate pass (dvh_certify.hip; dvh_options.certify, dvh_certify_batch): plain PDHG on the unscaled LP of every
 // on-chip window of the batch, one workgroup each, until a Farkas certificate (status 1, the ray in y) or an unbounded
@@ -304,6 +307,24 @@ hipError_t launch_pdhg_band_grid(const Batch& b, const Work& w, const Chunk& ch,
 // entry per window), the steps, the last-step candidates.  counts[5] (device, zeroed by the caller) = {windows
 // examined, primal infeasible, dual infeasible, skipped for size (n or m > kSmallMax), largest certificate-iteration
 // count}.  max_n, max_m: the largest on-chip window (the launch's LDS).
+//
+// dvh_options.certify = 2 adds the early exit inside the PDHG kernels that take POI windows (pdhg_kernel, every
+// instantiation; pdhg_band_grid_kernel), a compile-time flag on both, so levels 0 and 1 launch the instantiations they
+// always did.  At every KKT check, before the termination test, the scaled dual y~ of T(z_k) is put through the pass's
+// Farkas test.  With v = Dr y~ and kty = K~'y~ (which the check forms anyway; K~ = Dr K Dc, q~ = Dr q, l~ = l / Dc,
+// u~ = u / Dc) every term of the margin is scale-free:
+//     q'v = sum_i q~_i y~_i,   r = K'v = kty / Dc,   u_j r_j = u~_j kty_j,   l_j r_j = l~_j kty_j,
+// and only viol = max |kty_j| / Dc_j, over the columns whose bound on r_j's side is infinite (the tau columns of the
+// battery forms), needs a factor.  The >= rows of y~ are >= 0 by the projection.  The three conditions (margin > 0,
+// viol <= 1e-8 margin, margin >= 1e-9 (sum |q~_i y~_i| + sum |bound terms|)) are homogeneous in v, so v is normalised
+// only when they pass.  The sums and the maximum are block-reduced in a fixed order (no floating-point atomics), the
+// decision is uniform across the workgroup and every wave leaves at the same barrier.  A certified window gets what
+// the pass writes: status PRIMAL_INFEASIBLE, iters = the iteration of that check, y = v / ||v||_inf, stats {+inf,
+// margin, viol, 0} recomputed for that y with the double factors and the window's own q, l, u; x is the last checked
+// candidate and means nothing.  One lane adds the window to the handle's early counters {windows, largest iteration
+// count} (dvh_last_certify_early), which travel to the host with the pass's pinned word.  The pass still follows the
+// solve and skips such a window by its status.  The band, ICE, ELL, chain and grid-wide tiers ignore the level: their
+// windows keep the pass.  Unbounded rays are not tested in the kernels: dual-infeasible windows keep the pass too.
 constexpr int kCertifyDefaultCap = 65536;
 struct CertWork {
   int32_t* tptr;   // [sum n + count]

@@ -442,9 +442,13 @@ __host__ __device__ inline size_t pdhg_lds_bytes(int n, int m, int nnz, bool mld
   return s;
 }
 
-template <int B, int XS, int YS, bool MLDS>
+// CERT (dvh_options.certify = 2): the Farkas test of the scaled dual of T(z_k) at every KKT check, before the
+// termination test (the header comment of dvh_internal.h's certificate block has the scaled-space identities).  A
+// window that passes leaves the loop with status PRIMAL_INFEASIBLE at that check; early = {windows certified here,
+// their largest iteration count}, updated by one lane.  CERT = false compiles none of it.
+template <int B, int XS, int YS, bool MLDS, bool CERT = false>
 __global__ __launch_bounds__(B) void pdhg_kernel(const Batch b, const Work w, const Chunk ch, const Opts o,
-                                                 const int32_t* list) {
+                                                 const int32_t* list, int32_t* early) {
   constexpr int NW = B / kWave;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int k = list ? list[blockIdx.x] : ch.first + blockIdx.x;
@@ -686,6 +690,8 @@ __global__ __launch_bounds__(B) void pdhg_kernel(const Batch b, const Work w, co
     // ---------------- check: restart test; every kkt_every-th check also the KKT error of T(z) = (x+, y+)
     const bool kkt = (--kk == 0) || (it + chk > o.max_iters);
     if (kkt) kk = kkt_every;
+    double fk[3] = {0.0, 0.0, 0.0};  // CERT: sum of the bound terms of K~'y~, of their absolute values, sum |q~_i y~_i|
+    double fv = 0.0;                 // CERT: largest |(K'v)_j| on the side of an infinite bound
     if (kkt) {
 #pragma unroll
     for (int s = 0; s < XS; ++s)
@@ -707,6 +713,23 @@ __global__ __launch_bounds__(B) void pdhg_kernel(const Batch b, const Work w, co
       acc[6] += cj * xj;
       acc[8] += (fl ? loj * d * fmax(lam, 0.0) : 0.0) + (fh ? hij * d * fmin(lam, 0.0) : 0.0);
       acc[kRdx] += fabs(rd) * fabs(xj * d);
+      if constexpr (CERT) {
+        if (kty > 0.0) {
+          if (fh) {
+            fk[0] += hij * kty;
+            fk[1] += fabs(hij * kty);
+          } else {
+            fv = fmax(fv, kty / d);
+          }
+        } else if (kty < 0.0) {
+          if (fl) {
+            fk[0] += loj * kty;
+            fk[1] += fabs(loj * kty);
+          } else {
+            fv = fmax(fv, -kty / d);
+          }
+        }
+      }
     };
     auto row_kkt = [&](int i, double kx, double qi, double yi) {
       const double d = drv[i];
@@ -715,6 +738,7 @@ __global__ __launch_bounds__(B) void pdhg_kernel(const Batch b, const Work w, co
       acc[4] += r * r;
       acc[7] += qi * yi;
       acc[9] += (yi * d) * (yi * d);
+      if constexpr (CERT) fk[2] += fabs(qi * yi);
     };
 #pragma unroll
     for (int s = 0; s < XS; ++s) {
@@ -748,6 +772,16 @@ __global__ __launch_bounds__(B) void pdhg_kernel(const Batch b, const Work w, co
     }
     }
     block_sum<B, kNRed>(acc, red);
+    if constexpr (CERT) {
+      if (kkt) {  // (uniform: every wave takes the two reductions and leaves at the same barrier)
+        block_sum<B, 3>(fk, red);
+        const double viol = block_max<B>(fv, red);
+        if (farkas_passes(acc[7] - fk[0], viol, fk[2] + fk[1])) {
+          status = kPrimalInfeasible;
+          break;
+        }
+      }
+    }
     if (kkt) {
       const double pobj = acc[6] + c0, dobj = acc[7] + acc[8] + c0;
       const double pres = sqrt(acc[4]) / (1.0 + qnorm), dres = sqrt(acc[5]) / (1.0 + cnorm);
@@ -809,6 +843,60 @@ __global__ __launch_bounds__(B) void pdhg_kernel(const Batch b, const Work w, co
   for (int L = tid; L < nlt; L += B) {
     const int j = lxi[L];
     b.x[W.on + j] = unscale_x(lx[5 * kLMax + L], dcv[j], b.l[W.on + j], b.u[W.on + j]);
+  }
+  if constexpr (CERT) {
+    if (status == kPrimalInfeasible) {
+      // certified at the last check: Y still holds y~ of T(z_k).  y = v / ||v||_inf with v = Dr y~; the margin and the
+      // violation of that y on the unscaled window (double factors, the window's own q, l, u), as the after-pass
+      // reports them; x above is the last checked candidate and means nothing
+      double nv = 0.0;
+      for (int i = tid; i < m; i += B) nv = fmax(nv, fabs(Y[i] * drv[i]));
+      const double nrm = block_max<B>(nv, red);
+      double ea[2] = {0.0, 0.0};  // q'y, the bound terms of K'y
+      double ev = 0.0;
+      for (int i = tid; i < m; i += B) {
+        const double v = Y[i] * drv[i] / nrm;
+        yo_g[i] = v;
+        ea[0] += b.q[W.om + i] * v;
+      }
+      auto col_exit = [&](int j, double kty) {
+        const double r = kty / nrm / dcv[j];
+        const double lj = b.l[W.on + j], uj = b.u[W.on + j];
+        if (r > 0.0) {
+          if (uj < INFINITY) ea[1] += uj * r; else ev = fmax(ev, r);
+        } else if (r < 0.0) {
+          if (lj > -INFINITY) ea[1] += lj * r; else ev = fmax(ev, -r);
+        }
+      };
+#pragma unroll
+      for (int s = 0; s < XS; ++s) {
+        if (ts[s] >= 0) {
+          double kty = 0.0;
+          for (int p = ts[s]; p < te[s]; ++p) kty += M.tv[p] * Y[M.tc[p]];
+          col_exit(tid + s * B, kty);
+        }
+      }
+      for (int L = wid; L < nlt; L += NW) {
+        const int j = lxi[L];
+        double kty = 0.0;
+        for (int p = M.tp[j] + lane; p < M.tp[j + 1]; p += kWave) kty += M.tv[p] * Y[M.tc[p]];
+        kty = wave_sum(kty);
+        if (lane == 0) col_exit(j, kty);
+      }
+      block_sum<B, 2>(ea, red);
+      const double viol = block_max<B>(ev, red);
+      if (tid == 0) {
+        b.istats[2 * k] = kPrimalInfeasible;
+        b.istats[2 * k + 1] = it;
+        b.stats[4 * k] = INFINITY;
+        b.stats[4 * k + 1] = ea[0] - ea[1];
+        b.stats[4 * k + 2] = viol;
+        b.stats[4 * k + 3] = 0.0;
+        atomicAdd(&early[0], 1);
+        atomicMax(&early[1], it);
+      }
+      return;
+    }
   }
 #pragma unroll
   for (int s = 0; s < YS; ++s)
@@ -1635,13 +1723,14 @@ __global__ __launch_bounds__(B) __attribute__((amdgpu_waves_per_eu(WPE))) void p
   }
 }
 
+// early != null: the instantiation with the in-kernel Farkas test (dvh_options.certify = 2)
 template <int B, int XS, int YS, bool MLDS>
 hipError_t launch_one(const Batch& b, const Work& w, const Chunk& ch, const Opts& o, size_t lds, hipStream_t s,
-                      const int32_t* list, int nlist) {
-  auto kern = pdhg_kernel<B, XS, YS, MLDS>;
+                      const int32_t* list, int nlist, int32_t* early) {
+  auto kern = early ? pdhg_kernel<B, XS, YS, MLDS, true> : pdhg_kernel<B, XS, YS, MLDS, false>;
   hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3(list ? nlist : ch.count), dim3(B), lds, s, b, w, ch, o, list);
+  hipLaunchKernelGGL(kern, dim3(list ? nlist : ch.count), dim3(B), lds, s, b, w, ch, o, list, early);
   return hipGetLastError();
 }
 
@@ -1649,10 +1738,10 @@ hipError_t launch_one(const Batch& b, const Work& w, const Chunk& ch, const Opts
 // so windows with n, m <= 4096 run with the whole iterate in registers.
 template <bool MLDS>
 hipError_t dispatch_xy(int xs, int ys, const Batch& b, const Work& w, const Chunk& ch, const Opts& o, size_t lds,
-                       hipStream_t s, const int32_t* list, int nlist) {
+                       hipStream_t s, const int32_t* list, int nlist, int32_t* early) {
   constexpr int B = 512;
 #define DVH_CASE(X_, Y_) \
-  if (xs <= X_ && ys <= Y_) return launch_one<B, X_, Y_, MLDS>(b, w, ch, o, lds, s, list, nlist);
+  if (xs <= X_ && ys <= Y_) return launch_one<B, X_, Y_, MLDS>(b, w, ch, o, lds, s, list, nlist, early);
   DVH_CASE(2, 2)
   DVH_CASE(5, 3)
   DVH_CASE(6, 4)
@@ -1752,7 +1841,8 @@ hipError_t launch_power(const Batch& b, const Work& w, const Chunk& ch, const Op
 }
 
 hipError_t launch_pdhg(const Batch& b, const Work& w, const Chunk& ch, const Opts& o, int max_n, int max_m,
-                       int64_t max_nnz, hipStream_t s, int* variant_out, const int32_t* list, int nlist) {
+                       int64_t max_nnz, hipStream_t s, int* variant_out, const int32_t* list, int nlist,
+                       int32_t* early) {
   constexpr int B = 512;
   constexpr size_t kLdsCap = 160 * 1024;
   const int xs = (max_n + B - 1) / B, ys = (max_m + B - 1) / B;
@@ -1762,8 +1852,8 @@ hipError_t launch_pdhg(const Batch& b, const Work& w, const Chunk& ch, const Opt
   const size_t lds = mlds ? lds_m : pdhg_lds_bytes(max_n, max_m, 0, false, B / kWave);
   if (lds > kLdsCap) return hipErrorInvalidValue;
   if (variant_out) *variant_out = (mlds ? 1000 : 0) + xs * 10 + ys;
-  return mlds ? dispatch_xy<true>(xs, ys, b, w, ch, o, lds, s, list, nlist)
-              : dispatch_xy<false>(xs, ys, b, w, ch, o, lds, s, list, nlist);
+  return mlds ? dispatch_xy<true>(xs, ys, b, w, ch, o, lds, s, list, nlist, early)
+              : dispatch_xy<false>(xs, ys, b, w, ch, o, lds, s, list, nlist, early);
 }
 
 // Small windows (the daily market-service window: T = 24, n = 168, m <= 265, K^T rows <= 6, K rows <= 8; with

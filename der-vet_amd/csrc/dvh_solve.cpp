@@ -69,7 +69,7 @@ int certify_pass(dvh_handle* h, const dvh_packed* bt, const std::vector<int64_t>
   DVH_HIP(h, h->c_sig.ensure(D * (size_t)sm));
   DVH_HIP(h, h->c_gy.ensure(D * (size_t)sm));
   DVH_HIP(h, h->c_counts.ensure(I * 5));
-  DVH_HIP(h, h->cert_host.ensure(I * 5));
+  DVH_HIP(h, h->cert_host.ensure(I * 7));
   for (DevEvent& e : h->cert_ev) DVH_HIP(h, e.ensure());
   dvh::CertWork cw{h->c_tptr.as<int32_t>(), h->c_tind.as<int32_t>(), h->c_tval.as<double>(), h->c_tau.as<double>(),
                    h->c_gx.as<double>(), h->c_sig.as<double>(), h->c_gy.as<double>(), h->c_counts.as<int32_t>(),
@@ -80,12 +80,18 @@ int certify_pass(dvh_handle* h, const dvh_packed* bt, const std::vector<int64_t>
   DVH_HIP(h, dvh::launch_certify(make_batch(*bt), cw, count, mn, mm, cap, gate, s));
   DVH_HIP(h, hipEventRecord(h->cert_ev[1], s));
   DVH_HIP(h, hipMemcpyAsync(h->cert_host.p, h->c_counts.p, I * 5, hipMemcpyDeviceToHost, s));
+  // the in-kernel certificates' counters (certify = 2, after a solve) ride along: no wait of their own
+  h->cert_early_pending = gate && early_counters(h);
+  if (h->cert_early_pending)
+    DVH_HIP(h, hipMemcpyAsync(h->cert_host.as<int32_t>() + 5, h->c_early.p, I * 2, hipMemcpyDeviceToHost, s));
   h->cert_pending = true;
   return DVH_OK;
 }
 
 void certify_reset(dvh_handle* h) {
   for (int32_t& v : h->st.cert) v = 0;
+  h->st.cert_early[0] = h->st.cert_early[1] = 0;
+  h->cert_early_pending = false;
   h->st.cert_ms = 0.0;
   h->cert_pending = false;
 }
@@ -259,7 +265,8 @@ int host_list_tiers(dvh_handle* h, const dvh::Batch& b, const dvh::Work& w, cons
     DVH_HIP(h, hipMemcpyAsync(h->d_list.p, generic.data(), I * generic.size(), hipMemcpyHostToDevice, s));
     DVH_HIP(h, dvh::launch_power(b, w, c.ch, o, h->d_list.as<int32_t>(), (int)generic.size(), s));
     int gv = -1;
-    e = dvh::launch_pdhg(b, w, c.ch, o, c.mn, c.mm, c.mnz, s, &gv, h->d_list.as<int32_t>(), (int)generic.size());
+    e = dvh::launch_pdhg(b, w, c.ch, o, c.mn, c.mm, c.mnz, s, &gv, h->d_list.as<int32_t>(), (int)generic.size(),
+                         early_counters(h));
     if (e == hipErrorInvalidValue)
       return fail(h, DVH_ERR_UNSUPPORTED, "window too large for the on-chip PDHG kernels (n or m > 4096)");
     if (e != hipSuccess) return hip_fail(h, e, "launch_pdhg");
@@ -286,6 +293,10 @@ int solve_packed(dvh_handle* h, const dvh_packed* bt, const std::vector<int64_t>
   dvh::Work w;
   if (int rc = make_work(h, plan, w)) return rc;
   h->st.reset();
+  if (h->opts.certify >= 2) {  // the early exit's counters: the handle's, zeroed ahead of the kernels that feed them
+    DVH_HIP(h, h->c_early.ensure(sizeof(int32_t) * 2));
+    DVH_HIP(h, hipMemsetAsync(h->c_early.p, 0, sizeof(int32_t) * 2, s));
+  }
   DVH_HIP(h, hipEventRecord(h->ev[0], s));
   // dvh_set_launch_order: consumed by this solve; applied when it covers the batch, which is one chunk of small windows
   const size_t I = sizeof(int32_t);
@@ -349,6 +360,9 @@ int finish_timing(dvh_handle* h, hipStream_t s) {
   if (hipEventElapsedTime(&t, h->ev[0], h->ev[3]) == hipSuccess) st.timing[0] = t;
   if (h->cert_pending) {  // the certificate pass's counters and time (copied behind it on the stream)
     for (int i = 0; i < 5; ++i) st.cert[i] = h->cert_host.as<int32_t>()[i];
+    if (h->cert_early_pending)
+      for (int i = 0; i < 2; ++i) st.cert_early[i] = h->cert_host.as<int32_t>()[5 + i];
+    h->cert_early_pending = false;
     if (hipEventElapsedTime(&t, h->cert_ev[0], h->cert_ev[1]) == hipSuccess) st.cert_ms = t;
     h->cert_pending = false;
   }

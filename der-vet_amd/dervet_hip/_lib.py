@@ -179,6 +179,7 @@ SYMBOLS = {
     "dvh_certify_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(LP), ctypes.c_int32, ctypes.POINTER(Result)]),
     "dvh_last_certify": (ctypes.c_int, [ctypes.c_void_p, c_int32_p]),
     "dvh_last_certify_ms": (ctypes.c_int, [ctypes.c_void_p, c_double_p]),
+    "dvh_last_certify_early": (ctypes.c_int, [ctypes.c_void_p, c_int32_p]),
     "dvh_solve_packed_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Packed), ctypes.c_void_p]),
     "dvh_warm_transfer": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Packed), ctypes.c_void_p, ctypes.c_int32]),
     "dvh_warm_transfer_blend": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Packed), ctypes.c_void_p,

@@ -39,7 +39,8 @@ GPU certificates (``certify=True``, ``install(certify=True)``; off by default): 
 ``certify`` option (include/dervet_hip.h: the certificate pass behind every solve), and a window it returns as
 PRIMAL_INFEASIBLE / DUAL_INFEASIBLE -- a Farkas certificate or an unbounded ray that passed its test on the GPU -- is
 saved as ECOS would report it ("infeasible" / "unbounded") without the reference re-solve; ``LoopReport.certified``
-counts them (they count as ``gpu`` windows too).  Scenarios whose windows are coupled through
+counts them (they count as ``gpu`` windows too).  ``certify=2`` is forwarded as the option's level 2 (the early exit
+for infeasible windows inside the PDHG kernels; ``certify=True`` stays level 1); the saved results are the same.  Scenarios whose windows are coupled through
 saved results (battery degradation, Battery.py:87-110; sizing, MicrogridScenario.py:361-363) cannot batch their
 own windows; ``batched_cases_loop`` batches them ACROSS scenarios instead: window k of every case in one GPU
 call, saved before any case sets up window k + 1 (the serial case loop of dervet/DERVET.py:75-83, in lockstep).
@@ -192,17 +193,22 @@ def _restore_window_state(scenario, plan):
             der.variables_dict = vd
 
 
+def certify_level(certify):
+    """The dvh_options.certify level of a ``certify`` argument: False / 0 -> 0, True -> 1, an integer level as given."""
+    return int(certify)
+
+
 def _solve_plans(plans, solver, certify=False):
     """One batched solve over the LP windows of `plans` (list of plan tuples); returns {index: WindowResult}.
-    certify: the handle runs with the certificate pass behind the solve."""
+    certify: the handle runs with the certificate pass behind the solve (2: and the early exit inside the kernels)."""
     lp_idx = [i for i, p in enumerate(plans) if p.win is not None]
     if not lp_idx:
         return {}
     own = solver is None
     if own:
-        solver = BatchSolver(0, certify=1) if certify else BatchSolver(0)
+        solver = BatchSolver(0, certify=certify_level(certify)) if certify else BatchSolver(0)
     elif certify:
-        solver.set_options(certify=1)
+        solver.set_options(certify=certify_level(certify))
     try:
         res = solver.solve([plans[i].win.lp for i in lp_idx])
     finally:
@@ -273,7 +279,7 @@ def batched_cases_loop(scenarios, solver=None, exporter=None, relax_milp=False, 
     exporter = exporter or CvxpyExporter(relax_milp)
     own = solver is None
     if own:
-        solver = BatchSolver(0, certify=1) if certify else BatchSolver(0)
+        solver = BatchSolver(0, certify=certify_level(certify)) if certify else BatchSolver(0)
     try:
         live, indep, coupled = [], [], []
         for s in scenarios:
@@ -335,7 +341,9 @@ def make_batched_scenario_class(base, solver_factory=None, relax_milp=False, ret
 
     BatchedMicrogridScenario.__name__ = "BatchedMicrogridScenario"
     BatchedMicrogridScenario.dervet_hip_options = (solver_factory, bool(relax_milp), bool(retry_failed))
-    BatchedMicrogridScenario.dervet_hip_certify = bool(certify)  # (with dervet_hip_options: what install compares)
+    BatchedMicrogridScenario.dervet_hip_certify = bool(certify)
+    # (with dervet_hip_options: what install compares)
+    BatchedMicrogridScenario.dervet_hip_certify_level = certify_level(certify)
     return BatchedMicrogridScenario
 
 
@@ -394,8 +402,9 @@ def install(dervet_module=None, relax_milp=False, retry_failed=True, solver_fact
     """Patch dervet.DERVET.MicrogridScenario (hard-coded at dervet/DERVET.py:76) with the batched class.
     ``relax_milp``: the user's opt-in to GPU LP relaxations of binary = 1 windows (north_star); off, MILP windows stay
     on the reference solve.  ``retry_failed``: re-solve windows without a certified GPU optimum by the reference.
-    ``certify``: the solver factory's handle runs with the GPU certificate pass (``certify`` = 1) and a window it
-    certifies is saved as "infeasible" / "unbounded" without the reference re-solve (``LoopReport.certified``).
+    ``certify``: the solver factory's handle runs with the GPU certificate pass (``certify`` = 1; ``certify=2``: level
+    2, with the early exit inside the PDHG kernels) and a window it certifies is saved as "infeasible" / "unbounded"
+    without the reference re-solve (``LoopReport.certified``).  A different level re-installs.
     ``batch_cases``: also patch ``DERVET.solve`` (DERVET.py:72-90) so that every case's windows go to the GPU
     together (``make_batched_dervet_solve``; ``case_batch`` cases at a time); off, the reference's serial case loop
     is kept (and a previous ``batch_cases`` install is undone)."""
@@ -404,7 +413,7 @@ def install(dervet_module=None, relax_milp=False, retry_failed=True, solver_fact
     base = dervet_module.MicrogridScenario
     if getattr(base, "__name__", "") == "BatchedMicrogridScenario":
         if base.dervet_hip_options == (solver_factory, bool(relax_milp), bool(retry_failed)) and \
-                getattr(base, "dervet_hip_certify", False) == bool(certify):
+                getattr(base, "dervet_hip_certify_level", 0) == certify_level(certify):
             cls = base
         else:
             base = base.__bases__[0]  # re-install with the new options over the reference class

@@ -194,7 +194,9 @@ class BatchSolver:
         With the ``certify=1`` option, a window the cascade leaves ITER_LIMIT / NUMERICAL and the certificate pass
         proves infeasible or unbounded returns status "infeasible" / "unbounded", obj +inf / -inf, the normalised
         Farkas ray in y / the unbounded ray in x, primal_res_rel = the certificate's margin, dual_res_rel = its
-        violation (include/dervet_hip.h); ``certify_stats()`` counts them."""
+        violation (include/dervet_hip.h); ``certify_stats()`` counts them.  ``certify=2`` also tests inside the PDHG
+        kernels that take POI windows: an infeasible one stops at the KKT check that certifies it (``iters`` = that
+        iteration, x meaningless) instead of running to ``max_iters`` first."""
         return self._batch_call("dvh_solve_batch", lps, start)
 
     def certify(self, lps):
@@ -204,13 +206,18 @@ class BatchSolver:
         return self._batch_call("dvh_certify_batch", lps, None)
 
     def certify_stats(self):
-        """The certificate pass of the last solve / certify call (dvh_last_certify); all 0 when it did not run."""
+        """The certificate pass of the last solve / certify call (dvh_last_certify); all 0 when it did not run.
+        ``early`` / ``early_max_iters`` (dvh_last_certify_early): the windows the ``certify=2`` option's test inside
+        the PDHG kernels certified, which the pass never examined, and the largest iteration count among them."""
         v = (ctypes.c_int32 * 5)()
         self._check(self._lib.dvh_last_certify(self._h, v), "dvh_last_certify")
         ms = ctypes.c_double()
         self._check(self._lib.dvh_last_certify_ms(self._h, ctypes.byref(ms)), "dvh_last_certify_ms")
+        e = (ctypes.c_int32 * 2)()
+        if hasattr(self._lib, "dvh_last_certify_early"):  # (an A/B build of an earlier library has none)
+            self._check(self._lib.dvh_last_certify_early(self._h, e), "dvh_last_certify_early")
         return {"examined": v[0], "primal_infeasible": v[1], "dual_infeasible": v[2], "skipped": v[3],
-                "max_iters": v[4], "ms": float(ms.value)}
+                "max_iters": v[4], "ms": float(ms.value), "early": e[0], "early_max_iters": e[1]}
 
     def _batch_call(self, entry, lps, start):
         count = len(lps)

@@ -89,6 +89,14 @@ typedef struct dvh_options {
                               /* on-chip windows that came back ITER_LIMIT or NUMERICAL, in one launch gated on    */
                               /* the device (no extra host wait): a window it certifies returns PRIMAL_INFEASIBLE  */
                               /* or DUAL_INFEASIBLE with its ray, every other window is left exactly as it was     */
+                              /* 2: everything 1 means, plus an early exit inside the PDHG kernels that take       */
+                              /* POI windows (the generic kernel; the band kernel's interconnection form): at every */
+                              /* KKT check the dual of T(z_k) is put through the Farkas test below, and a window    */
+                              /* that passes stops there as PRIMAL_INFEASIBLE with iters = that check's iteration,  */
+                              /* its ray in y, stats as the pass writes them and an x that means nothing.  The      */
+                              /* pass still follows and skips such a window by its status.  The battery band, ICE,  */
+                              /* ELL, chain and grid-wide tiers ignore the level (their windows keep the pass), as  */
+                              /* do unbounded windows.  Feasible windows return what levels 0 and 1 return.         */
 } dvh_options;
 
 typedef struct dvh_lp {
@@ -334,6 +342,10 @@ int dvh_certify_batch(dvh_handle* h, const dvh_lp* lps, int32_t count, dvh_resul
 int dvh_last_certify(const dvh_handle* h, int32_t* out5);
 /* Its kernel time (HIP events, milliseconds; 0 when it did not run). */
 int dvh_last_certify_ms(const dvh_handle* h, double* ms);
+/* dvh_options.certify = 2: out2 = {windows of the most recent solve certified inside a PDHG kernel, the largest
+ * iteration count among them}.  They are not among dvh_last_certify's counts: the pass never examined them.  Both 0
+ * below level 2; reset by every solve. */
+int dvh_last_certify_early(const dvh_handle* h, int32_t* out2);
 
 /* Timing of the most recent solve on the handle's stream (HIP events, milliseconds):
  * [0] whole solve, [1] setup kernel (transpose + scaling + power iteration), [2] PDHG kernels.  On the default

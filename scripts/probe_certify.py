@@ -2,10 +2,12 @@
 """The certificate pass (csrc/dvh_certify.hip, dvh_options.certify) on a sweep with infeasible windows: 768 monthly POI
 windows (builder.battery_group, T = 744, one demand period) of which 77 are made infeasible -- an overloaded step, a
 month short of energy under the import limit, a minimum SOE the charger cannot reach, in turn.  Per kernel path
-(default, interconnect): wall of the solve with certify 0 and 1 (best of 3 after a warm-up), statuses, the pass's
-own time (HIP events) and counts; then the screen (BatchSolver.certify) over the same windows and the histogram of
-its certificate-iteration counts.  With DVH_LIB naming an earlier build of the library (no certificate pass) only the
-certify = 0 solves run: the parent commit's time for the same batch.
+(default, interconnect): wall of the solve with certify 0, 1 and 2 (five timed repeats after a warm-up: fastest,
+median, slowest), statuses, the pass's own time (HIP events) and counts, the in-kernel certificates of level 2; then
+the screen (BatchSolver.certify) over the same windows and the histogram of its certificate-iteration counts.  With
+DVH_LIB naming an earlier build of the library only the levels it knows run (none: certify = 0; no
+dvh_last_certify_early: 0 and 1) and the screen is left out: the parent commit's times for the same batch, to be
+taken in the same job.  [infeasible] = 0 gives the all-feasible sweep.
 
 Usage: python scripts/probe_certify.py [windows] [infeasible]
 """
@@ -54,32 +56,37 @@ def main(argv):
     dev = pb.to_torch("cuda:0").alloc_outputs()
     s = BatchSolver(0)
     has_pass = hasattr(s._lib, "dvh_certify_batch") and hasattr(s._opts, "certify")
+    has_early = has_pass and hasattr(s._lib, "dvh_last_certify_early")
+    levels = (0, 1, 2) if has_early else (0, 1) if has_pass else (0,)
     print(json.dumps({"windows": pb.count, "infeasible": len(kinds), "n": g.n, "m": g.m,
-                      "library": os.environ.get("DVH_LIB", "in-tree"), "certificate_pass": has_pass}), flush=True)
+                      "library": os.environ.get("DVH_LIB", "in-tree"), "certificate_pass": has_pass,
+                      "levels": levels}), flush=True)
     for path in ("default", "interconnect"):
         s.set_kernel_path(path)
-        for certify in ((0, 1) if has_pass else (0,)):
+        for certify in levels:
             if has_pass:
                 s.set_options(certify=certify)
             s.solve_packed(dev)
             ts = []
-            for _ in range(3):
+            for _ in range(5):
                 torch.cuda.synchronize()
                 t = time.perf_counter()
                 s.solve_packed(dev)
                 torch.cuda.synchronize()
                 ts.append(time.perf_counter() - t)
             ist = dev.istats.cpu().numpy()
-            out = {"path": path, "certify": certify, "ms": round(1e3 * min(ts), 2), "gpu_ms": s.timing(),
+            ts.sort()
+            out = {"path": path, "certify": certify, "ms": round(1e3 * ts[0], 2), "ms_median": round(1e3 * ts[2], 2),
+                   "ms_max": round(1e3 * ts[-1], 2), "gpu_ms": s.timing(),
                    "status_counts": {int(k): int(v) for k, v in zip(*np.unique(ist[:, 0], return_counts=True))},
                    "bad_status_counts": {int(k): int(v) for k, v in
-                                         zip(*np.unique(ist[sorted(kinds), 0], return_counts=True))},
+                                         zip(*np.unique(ist[np.array(sorted(kinds), int), 0], return_counts=True))},
                    "iters_max": int(ist[:, 1].max()), "host_syncs": s.host_syncs()}
             if has_pass:
                 out["pass"] = s.certify_stats()
             print(json.dumps(out), flush=True)
     s.set_kernel_path("default")
-    if has_pass:
+    if has_pass and not os.environ.get("DVH_LIB"):
         lps = builder.group_window_lps(g)
         t = time.perf_counter()
         res = s.certify(lps)
