@@ -298,6 +298,13 @@ hipError_t large_solve(LargeSolver* ls, const Batch& b, int k, const int64_t* d,
 hipError_t launch_pdhg_band_grid(const Batch& b, const Work& w, const Chunk& ch, const Opts& o, hipStream_t s,
                                  const int32_t* list, int nlist, int* variant_out, int32_t* early = nullptr);
 
+// The band kernel's load-shift form (dvh_band_shift.hip; dvh_set_kernel_path 6): battery windows with a controllable
+// load (two more column blocks pw, el and T + D more equality rows), one workgroup per listed window.  As the
+// interconnection form, a workgroup returns at once unless its window's status is -2 (kNeedsEll), so the launch follows
+// the ICE pass over the same list; windows it refuses keep status -2.  variant_out: 9000000 + 300 + waves per window.
+hipError_t launch_pdhg_band_shift(const Batch& b, const Work& w, const Chunk& ch, const Opts& o, hipStream_t s,
+                                  const int32_t* list, int nlist, int* variant_out);
+
 // Certificate pass (dvh_certify.hip; dvh_options.certify, dvh_certify_batch): plain PDHG on the unscaled LP of every
 // on-chip window of the batch, one workgroup each, until a Farkas certificate (status 1, the ray in y) or an unbounded
 // ray (status 2, the ray in x) passes its test or `cap` iterations are done.  gate != 0 (after a solve): a workgroup

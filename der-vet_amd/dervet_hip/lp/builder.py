@@ -39,6 +39,7 @@ class WindowGroup:
     terms: dict = field(default_factory=dict)   # key -> (coef [G, n], const [G])
     tags: list = field(default_factory=list)    # per-window identifiers (scenario, window)
     inputs: dict = None     # battery_group: the compact series the bill reads (valuation.BillInputs fields)
+    ctrl_load: dict = None  # battery_group with a controllable load: rated_power [G], duration [G], day_starts
 
     @property
     def G(self):
@@ -62,7 +63,7 @@ def _col(a, G, T=None):
 
 def battery_group(T, dt, base_load, bat, retail_price=None, da_price=None, demand_masks=None, demand_prices=None,
                   ene_min=None, ene_max=None, name="es", tags=None, pv_curtail_max=None, ice=None, poi=None,
-                  grid_charge=True, pv_gen=None):
+                  grid_charge=True, pv_gen=None, ctrl_load=None):
     """Build G windows sharing T steps and the demand masks.
 
     base_load [G, T]  : site load minus fixed generation (kW), hp is added here from ``bat``
@@ -83,9 +84,19 @@ def battery_group(T, dt, base_load, bat, retail_price=None, da_price=None, deman
     grid_charge       : False = PV grid_charge 0 (Schema.json:1875): the battery charges from PV only, ch_t <= pv_gen_t
                       (+ pv_t if curtailable); with fixed PV only it tightens ch's upper bound (UNPINNED)
     pv_gen [G, T]     : the fixed PV generation inside base_load (for grid_charge = False)
+    ctrl_load         : dict rated_power (kW), duration (h), scalars or [G], and day_starts (sorted step indices, the
+                      first one 0, shared by the group): a controllable (load-shifting) load, dervet
+                      MicrogridDER/LoadControllable.py:215-251 (``_add_ctrl_load``; UNPINNED).  Duration 0 everywhere is
+                      a plain load: no block.  Not combined with ice, poi, pv_curtail_max or grid_charge = False.
     Variable order [ch, dis, ene, tau, pv?, elec?, on?]; >= rows: DCM epigraph, per step the two ICE rows, the POI
     import rows, the POI export rows, the charge-from-PV rows (grid_charge = False with curtailable PV).
     """
+    if ctrl_load is not None and np.any(np.asarray(ctrl_load["duration"], np.float64) != 0.0):
+        if ice is not None or poi is not None or pv_curtail_max is not None or not grid_charge:
+            raise NotImplementedError("battery_group: a controllable load is not combined with ice, poi, "
+                                      "pv_curtail_max or grid_charge = False")
+    else:
+        ctrl_load = None
     base_load = np.atleast_2d(np.asarray(base_load, np.float64))
     G = base_load.shape[0]
     masks = np.zeros((0, T), bool) if demand_masks is None else np.asarray(demand_masks, bool)
@@ -254,8 +265,89 @@ def battery_group(T, dt, base_load, bat, retail_price=None, da_price=None, deman
                   om=_col(bat.get("OMexpenses", 0.0), G), has_pv=ipv >= 0,
                   ice_cost=None if ice is None else (_col(ice["efficiency"], G) * _col(ice["fuel_cost"], G)
                                                      + _col(ice.get("variable_om_cost", 0.0), G)) * dt)
-    return WindowGroup(T=T, J=J, m_eq=T + 1, indptr=indptr.astype(np.int32), indices=indices, data=data, c=c, c0=c0,
-                       q=q, l=l, u=u, terms=terms, tags=list(tags) if tags is not None else [None] * G, inputs=inputs)
+    g = WindowGroup(T=T, J=J, m_eq=T + 1, indptr=indptr.astype(np.int32), indices=indices, data=data, c=c, c0=c0,
+                    q=q, l=l, u=u, terms=terms, tags=list(tags) if tags is not None else [None] * G, inputs=inputs)
+    if ctrl_load is not None:
+        g = _add_ctrl_load(g, dt, ctrl_load, retail_price, da_price)
+    return g
+
+
+def _add_ctrl_load(g, dt, ctrl_load, retail_price, da_price):
+    """The plain battery group ``g`` with a controllable load (dervet MicrogridDER/LoadControllable.py:215-251, the
+    sub-timestep variables left out: they are zero without market services).  With P the rated power, E_L = P x
+    duration and the window split into days [d0, d1) at ``day_starts``:
+
+      x = [ch, dis, ene, tau, pw(T), el(T)]          pw: the load offset (> 0 adds load), el: the load's energy state
+      bounds           -P <= pw <= P, 0 <= el <= E_L                                           (:234-237)
+      equality rows after the battery's T + 1, day by day                                     (:242-249)
+                       el_d0 = E_L
+                       el_t + dt pw_t - el_{t+1} = 0          t = d0 .. d1 - 2
+                       el_{d1-1} + dt pw_{d1-1} = E_L
+      net load         every DCM epigraph row gains -pw_t; the retail / DA terms gain price_t dt pw_t under keys of
+                       their own ('ctrl_load retailETS', 'ctrl_load DA')                       (get_charge, :120-133)
+
+    The group carries no ``inputs``: valuation, the device builder and economic sizing do not take these windows."""
+    G, T, J = g.G, g.T, g.J
+    P = _col(ctrl_load["rated_power"], G)
+    EL = P * _col(ctrl_load["duration"], G)
+    ds = np.asarray(ctrl_load["day_starts"], np.int64).ravel()
+    if len(ds) == 0 or ds[0] != 0 or np.any(np.diff(ds) <= 0) or ds[-1] >= T:
+        raise ValueError("ctrl_load day_starts: sorted step indices inside the window, the first one 0")
+    D = len(ds)
+    ends = np.append(ds[1:], T)
+    n0 = g.n
+    ipw, iel, n = n0, n0 + T, n0 + 2 * T
+    # the load's equality rows (columns sorted: pw_t < el_t < el_{t+1})
+    l_idx, l_val, l_len = [], [], []
+    ql = np.zeros((G, T + D))
+    r = 0
+    for d0, d1 in zip(ds, ends):
+        l_idx.append([iel + d0])
+        l_val.append([1.0])
+        l_len.append(1)
+        ql[:, r] = EL
+        r += 1
+        for t in range(d0, d1 - 1):
+            l_idx.append([ipw + t, iel + t, iel + t + 1])
+            l_val.append([dt, 1.0, -1.0])
+            l_len.append(3)
+            r += 1
+        l_idx.append([ipw + d1 - 1, iel + d1 - 1])
+        l_val.append([dt, 1.0])
+        l_len.append(2)
+        ql[:, r] = EL
+        r += 1
+    l_idx = np.concatenate([np.asarray(v, np.int64) for v in l_idx])
+    l_val = np.concatenate([np.asarray(v, np.float64) for v in l_val])
+    # the DCM rows gain -pw_t (their last column)
+    p_eq = int(g.indptr[T + 1])
+    mI = g.m - (T + 1)
+    dcm_t = g.inputs["dcm_t"].astype(np.int64)
+    d_idx = np.concatenate([g.indices[p_eq:].reshape(mI, 3).astype(np.int64), (ipw + dcm_t)[:, None]], axis=1)
+    d_val = np.concatenate([g.data[:, p_eq:].reshape(G, mI, 3), np.full((G, mI, 1), -1.0)], axis=2)
+    lens = np.concatenate([np.diff(g.indptr[:T + 2]), l_len, np.full(mI, 4)]).astype(np.int64)
+    indptr = np.zeros(len(lens) + 1, np.int64)
+    np.cumsum(lens, out=indptr[1:])
+    indices = np.concatenate([g.indices[:p_eq].astype(np.int64), l_idx, d_idx.ravel()]).astype(np.int32)
+    data = np.concatenate([g.data[:, :p_eq], np.broadcast_to(l_val, (G, len(l_val))), d_val.reshape(G, -1)], axis=1)
+    q = np.concatenate([g.q[:, :T + 1], ql, g.q[:, T + 1:]], axis=1)
+    l = np.concatenate([g.l, -P[:, None] * np.ones((1, T)), np.zeros((G, T))], axis=1)
+    u = np.concatenate([g.u, P[:, None] * np.ones((1, T)), EL[:, None] * np.ones((1, T))], axis=1)
+    pad = np.zeros((G, 2 * T))
+    terms = {k: (np.concatenate([coef, pad], axis=1), const) for k, (coef, const) in g.terms.items()}
+    for key, price in (("DA", da_price), ("retailETS", retail_price)):
+        if price is not None:
+            coef = np.zeros((G, n))
+            coef[:, ipw:ipw + T] = _col(price, G, T) * dt
+            terms[f"ctrl_load {key}"] = (coef, np.zeros(G))
+    c = np.zeros((G, n))
+    c0 = np.zeros(G)
+    for coef, const in terms.values():
+        c += coef
+        c0 += const
+    return WindowGroup(T=T, J=J, m_eq=2 * T + 1 + D, indptr=indptr.astype(np.int32), indices=indices,
+                       data=np.ascontiguousarray(data), c=c, c0=c0, q=q, l=l, u=u, terms=terms, tags=g.tags, inputs=None,
+                       ctrl_load=dict(rated_power=P, duration=_col(ctrl_load["duration"], G), day_starts=ds))
 
 
 def _assemble(G, m, blocks):

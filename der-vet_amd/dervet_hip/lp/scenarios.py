@@ -44,13 +44,16 @@ def tariff(name="data_tariff"):
 
 def windows_by_period(year, dt, load, gen, bat, tariff_def=None, da_price=None, n="month", ene_min=None,
                       ene_max=None, demand_price_override=None, price_scale=None, tags_prefix=None,
-                      pv_curtail_max=None, ice=None, poi=None, grid_charge=True, only=None, spec=False):
+                      pv_curtail_max=None, ice=None, poi=None, grid_charge=True, only=None, spec=False,
+                      ctrl_load=None):
     """Split S scenarios' series [S, Tall] into windows; returns a list of WindowGroup (one per window id).
 
     demand_price_override [S] replaces every demand charge's $/kW (sweep); price_scale [S] scales energy prices.
     poi / grid_charge: POI interconnection limits and PV grid_charge (builder.battery_group; parity unpinned).
     only: window ids to build (None: all), e.g. one window position of a degradation-coupled sweep.
     spec: return the device builder's inputs (gpu_builder.BatteryGroupSpec) instead of host-built groups.
+    ctrl_load: dict rated_power, duration (scalars or [S]): a controllable load (builder.battery_group; parity
+    unpinned); each window's day_starts are the steps at which the calendar's day of year changes inside it.
     """
     load = np.atleast_2d(np.asarray(load, np.float64))
     S, Tall = load.shape
@@ -69,12 +72,17 @@ def windows_by_period(year, dt, load, gen, bat, tariff_def=None, da_price=None, 
         wid = yr - yr[0]
     else:
         wid = np.arange(Tall) // int(n)
+    day = (np.round(np.arange(Tall) * dt * 60.0).astype(np.int64) // 1440) if ctrl_load is not None else None
     groups = []
     for w in np.unique(wid):
         if only is not None and int(w) not in only:
             continue
         sel = np.nonzero(wid == w)[0]
         T = len(sel)
+        extra = {}
+        if ctrl_load is not None:
+            extra["ctrl_load"] = dict(rated_power=ctrl_load["rated_power"], duration=ctrl_load["duration"],
+                                      day_starts=np.concatenate([[0], 1 + np.nonzero(np.diff(day[sel]))[0]]))
         masks, prices = [], []
         for p in range(len(d_vals)):
             for mo in np.unique(month[sel]):
@@ -97,7 +105,7 @@ def windows_by_period(year, dt, load, gen, bat, tariff_def=None, da_price=None, 
             ene_max=None if ene_max is None else np.broadcast_to(ene_max, (S, Tall))[:, sel],
             tags=[(s if tags_prefix is None else tags_prefix[s], int(w)) for s in range(S)],
             pv_curtail_max=None if pv_curtail_max is None else np.broadcast_to(pv_curtail_max, (S, Tall))[:, sel],
-            ice=ice, poi=poi, grid_charge=grid_charge, pv_gen=None if grid_charge else gen[:, sel])
+            ice=ice, poi=poi, grid_charge=grid_charge, pv_gen=None if grid_charge else gen[:, sel], **extra)
         g.index = sel
         groups.append(g)
     return groups
@@ -203,12 +211,13 @@ def _config4_series(scenarios):
     return P, load, gen
 
 
-def config4(scenarios, n="month", dt=1.0, E=None, only=None, spec=False):
+def config4(scenarios, n="month", dt=1.0, E=None, only=None, spec=False, ctrl_load=None):
     """Synthetic sweep windows for the given scenario ids (12 monthly windows each).  n: the optimisation window
     (Model_Parameters_Template_DER.csv:8 `n`: "month", "year" or a step count); dt < 1: sub-hourly steps, the hourly
     series held constant within each hour (Model_Parameters_Template_DER.csv:4 `dt`).  E [S]: the batteries'
     current energy capacity (a degraded battery, dervet_hip.degradation; power ratings stay at the rated E /
-    duration); only: window ids to build; spec: the device builder's inputs instead of host-built groups."""
+    duration); only: window ids to build; spec: the device builder's inputs instead of host-built groups;
+    ctrl_load: as windows_by_period's (``config4_load_shift``)."""
     P, load, gen = _config4_series(tuple(int(s) for s in scenarios))
     Eb = P["E"] if E is None else np.asarray(E, np.float64)
     bat = dict(E=Eb, Pch=P["E"] / P["duration"], Pdis=P["E"] / P["duration"], rte=P["rte"], sdr=0.0,
@@ -217,7 +226,14 @@ def config4(scenarios, n="month", dt=1.0, E=None, only=None, spec=False):
     if rep > 1:
         load, gen = np.repeat(load, rep, axis=1), np.repeat(gen, rep, axis=1)
     return windows_by_period(2017, dt, load, gen, bat, tariff_def=tariff(), n=n, demand_price_override=P["demand"],
-                             price_scale=P["price_scale"], tags_prefix=list(scenarios), only=only, spec=spec)
+                             price_scale=P["price_scale"], tags_prefix=list(scenarios), only=only, spec=spec,
+                             **({} if ctrl_load is None else {"ctrl_load": ctrl_load}))
+
+
+def config4_load_shift(scenarios, rated_power=150.0, duration=4.0, n="month", only=None):
+    """The config-4 population with a controllable (load-shifting) load next to every battery: rated_power (kW) and
+    duration (h), scalars or one value per scenario (dervet MicrogridDER/LoadControllable.py; parity unpinned)."""
+    return config4(scenarios, n=n, only=only, ctrl_load=dict(rated_power=rated_power, duration=duration))
 
 
 def reliability_min_soe(critical_load, hours=4.0, dt=1.0, cap=None):

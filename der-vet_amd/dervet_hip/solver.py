@@ -167,6 +167,8 @@ class BatchSolver:
         return int(v.value)
 
     _PATHS = {"default": 0, "generic": 1, "ell": 2, "band1": 3, "band3": 4, "interconnect": 5}
+    # modes added after the six above, which tests/test_interconnect_path.py pins as a set: 6 the load-shift form
+    _MORE_PATHS = {"load_shift": 6}
 
     def set_kernel_path(self, path):
         """Kernel cascade: "default" (battery-banded -> ELL -> generic CSR), "ell" (ELL -> generic), "generic",
@@ -174,8 +176,10 @@ class BatchSolver:
         threads / three steps per lane, 256 threads, two windows per CU; the default picks one-step for batches of
         at most one battery window per CU), or "interconnect" (the default cascade plus the band kernel's
         interconnection form: windows with POI limit rows, a curtailable-PV block or charge-from-PV rows count as
-        band windows instead of ending on the generic kernel).  A bool selects "generic" (True) / "default" (False)."""
-        mode = (1 if path else 0) if isinstance(path, bool) else self._PATHS[path]
+        band windows instead of ending on the generic kernel), or "load_shift" (the default cascade plus the band
+        kernel's load-shift form: windows with a controllable load, ``builder.battery_group(ctrl_load=...)``, count
+        as band windows instead of ending on the ELL / generic kernels).  A bool selects "generic" (True) / "default" (False)."""
+        mode = (1 if path else 0) if isinstance(path, bool) else {**self._PATHS, **self._MORE_PATHS}[path]
         self._check(self._lib.dvh_set_kernel_path(self._h, mode), "dvh_set_kernel_path")
 
     def set_launch_order(self, order):

@@ -102,6 +102,8 @@ def bill_inputs(g, orig=None):
         return BillInputs(T=g.T, J=g.J, dt=g.dt, dcm_t=g.dcm_t, dcm_j=g.dcm_j, base=g.base, retail=g.retail, da=g.da,
                           demand=g.demand, om=g.scal["om"], ice_cost=g.ice["cost"] if g.ice else None, orig=orig)
     inp = getattr(g, "inputs", None)
+    if getattr(g, "ctrl_load", None) is not None:
+        raise NotImplementedError("bill: windows with a controllable load are not valued")
     if inp is None:
         raise ValueError("bill: the window group carries no series (builder.battery_group records them in .inputs)")
     return BillInputs(**inp, orig=orig)

@@ -748,7 +748,12 @@ int dvh_value_master(dvh_handle* h, const dvh_value_master_args* args, void* str
  * windows with POI import / export limit rows, a curtailable-PV column block (x = [ch, dis, ene, tau, pv]) and / or
  * charge-from-PV rows (PV grid_charge = 0), which the default cascade hands down to the generic CSR kernel, are
  * taken after the ICE pass by a 768-thread kernel of their own and counted as band windows; every other window lands
- * where mode 0 puts it, and the mode adds no host wait. */
+ * where mode 0 puts it, and the mode adds no host wait.  6 = as 0 plus the band kernel's load-shift form (opt-in):
+ * battery windows with a controllable load (x = [ch, dis, ene, tau, pw, el], the battery's T + 1 equality rows followed
+ * by the load's T + D: per day the day-start row, the el recurrence and the day-end row; every DCM row may carry
+ * pw_t), which mode 0 leaves to the ELL / generic kernels, are taken after the ICE pass by a 768-thread kernel of
+ * their own and counted as band windows, as mode 5 does for its windows; dvh_options.kkt_predict is ignored by that
+ * kernel and certify works through the after-pass.  One form is added at a time: mode 6 does not run mode 5's. */
 int dvh_set_kernel_path(dvh_handle* h, int mode);
 
 /* Launch order of the next solve (scheduling only: the results do not depend on it).  order: host array, a
