@@ -2,6 +2,7 @@
 // (dvh_sweep.hip), the scenario series generator (dvh_series.hip) and the device builder (dvh_build.hip).
 #include <cmath>
 
+#include "dvh_build_validate.h"
 #include "dvh_handle.h"
 
 extern "C" {
@@ -117,8 +118,16 @@ int dvh_build_battery_group(dvh_handle* h, const dvh_battery_group* g, const dvh
   if ((g->mI > 0 && (!g->dcm_t || !g->dcm_j)) || !g->base || (g->J > 0 && !g->demand) || !g->E || !g->pch ||
       !g->pdis || !g->rte || !g->sdr || !g->soc_target || !g->ulsoc || !g->llsoc || !g->om || !g->c0 ||
       (g->has_retail && !g->retail) || (g->has_da && !g->da) || (g->has_emin && !g->emin) ||
-      (g->has_emax && !g->emax) || (g->has_ice && (!g->ice_cap || !g->ice_pmin || !g->ice_cost)))
+      (g->has_emax && !g->emax) || (g->has_ice && (!g->ice_cap || !g->ice_pmin || !g->ice_cost)) ||
+      (g->has_ev && (!g->ev_ch_max || !g->ev_target || !g->ev_code)))
     return fail(h, DVH_ERR_ARG, "battery group: null input array");
+  if (g->has_ev && g->has_ice) return fail(h, DVH_ERR_ARG, "battery group: an EV is not combined with the ICE");
+  // the EV's step codes (a host array) decide where its rows go: validated and scanned before anything is launched
+  dvh::EvScan ev;
+  if (g->has_ev) {
+    const std::string msg = dvh::scan_ev_codes(g->ev_code, g->T, &ev);
+    if (!msg.empty()) return fail(h, DVH_ERR_ARG, msg);
+  }
   if (!b->desc || !b->indptr || !b->indices || !b->data || !b->c || !b->c0 || !b->q || !b->l || !b->u)
     return fail(h, DVH_ERR_ARG, "null device array in packed batch");
   DVH_HIP(h, hipSetDevice(h->device));
@@ -135,23 +144,29 @@ int dvh_build_battery_group(dvh_handle* h, const dvh_battery_group* g, const dvh
     DVH_HIP(h, hipMemcpyAsync(dt_.data(), g->dcm_t, sizeof(int32_t) * dt_.size(), hipMemcpyDefault, s));
     DVH_HIP(h, hipMemcpyAsync(dj_.data(), g->dcm_j, sizeof(int32_t) * dj_.size(), hipMemcpyDefault, s));
   }
+  if (g->has_ev) {  // (stream-ordered behind an earlier group's kernel, which reads the same buffer)
+    DVH_HIP(h, h->g_ev.ensure(sizeof(int32_t) * ev.tab.size()));
+    DVH_HIP(h, hipMemcpyAsync(h->g_ev.p, ev.tab.data(), sizeof(int32_t) * ev.tab.size(), hipMemcpyHostToDevice, s));
+  }
   DVH_HIP(h, hipStreamSynchronize(s));
   for (int32_t i = 0; i < g->mI; ++i)
     if (dt_[i] < 0 || dt_[i] >= g->T || dj_[i] < 0 || dj_[i] >= g->J)
       return fail(h, DVH_ERR_ARG, "battery group: demand-charge row " + std::to_string(i) + " (step " +
                                       std::to_string(dt_[i]) + ", column " + std::to_string(dj_[i]) +
                                       ") outside T = " + std::to_string(g->T) + ", J = " + std::to_string(g->J));
-  const bool ice = g->has_ice != 0;
-  const int64_t T = g->T, n = (ice ? 5 : 3) * T + g->J, m = T + 1 + g->mI + (ice ? 2 * T : 0),
-                nnz = 4 * T + (ice ? 4 : 3) * (int64_t)g->mI + (ice ? 4 * T : 0);
+  const bool ice = g->has_ice != 0, wide = ice || g->has_ev;
+  const int64_t T = g->T, n = (wide ? 5 : 3) * T + g->J, meq = T + 1 + (g->has_ev ? T + ev.D : 0),
+                m = meq + g->mI + (ice ? 2 * T : 0),
+                nnz = 4 * T + (wide ? 4 : 3) * (int64_t)g->mI + (ice ? 4 * T : 0) + ev.nnz;
   for (int w = 0; w < g->G; ++w) {
     const int64_t* d = &desc[8 * (size_t)w];
-    if (d[0] != n || d[1] != m || d[2] != T + 1 || d[3] != nnz || d[4] < 0 || d[5] < 0 || d[6] < 0 || d[7] < 0 ||
+    if (d[0] != n || d[1] != m || d[2] != meq || d[3] != nnz || d[4] < 0 || d[5] < 0 || d[6] < 0 || d[7] < 0 ||
         d[4] + m + 1 > b->total_rows || d[5] + nnz > b->total_nnz || d[6] + n > b->total_n || d[7] + m > b->total_m)
       return fail(h, DVH_ERR_ARG, "battery group: descriptor of window " + std::to_string(first + w) +
                                       " does not match the group's LP shape or the arrays");
   }
-  hipError_t e = dvh::launch_build_battery(*g, *b, first, s);
+  const dvh::EvLayout lay{g->has_ev ? h->g_ev.as<int32_t>() : nullptr, ev.D, ev.nnz, ev.n_trail};
+  hipError_t e = dvh::launch_build_battery(*g, lay, *b, first, s);
   if (e != hipSuccess) return hip_fail(h, e, "launch_build_battery");
   return DVH_OK;
 }

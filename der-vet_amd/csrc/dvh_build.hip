@@ -7,6 +7,10 @@
 // generated from (T, J, the demand-charge rows' steps and columns).  has_ice: the LP-relaxed ICE of battery_group's
 // `ice` (columns elec_t, on_t after tau; the DCM rows gain elec_t; two >= rows per step after the DCM rows:
 // cap on_t - elec_t >= 0, elec_t - pmin on_t >= 0; the fuel term last in the objective) -- BASELINE config 5.
+// has_ev: one electric vehicle of battery_group's `ev` (columns ev_ch_t, ev_ene_t after tau; after the battery's T + 1
+// equality rows, step by step, an optional start row and the step's load row; the DCM rows gain -ev_ch_t).  Where the
+// step's rows and entries go comes from the host's scan of the step codes (dvh_build_validate.h), checked again here
+// against the window's shape before anything is written through it.
 #include <math.h>
 
 #include "../../include/dervet_hip.h"
@@ -19,7 +23,8 @@ namespace {
 
 constexpr int kBuildB = 256;
 
-__global__ __launch_bounds__(kBuildB) void build_battery_kernel(const dvh_battery_group g, const int64_t* desc,
+__global__ __launch_bounds__(kBuildB) void build_battery_kernel(const dvh_battery_group g, const EvLayout ev,
+                                                               const int64_t* desc,
                                                                int32_t* indptr, int32_t* indices, double* data,
                                                                double* c, double* c0, double* q, double* l,
                                                                double* u, int first) {
@@ -27,10 +32,11 @@ __global__ __launch_bounds__(kBuildB) void build_battery_kernel(const dvh_batter
   const int k = first + w;
   const int64_t* d = desc + 8 * (int64_t)k;
   const int T = g.T, J = g.J, mI = g.mI;
-  const bool ice = g.has_ice != 0;
-  const int n = (ice ? 5 : 3) * T + J, m = T + 1 + mI + (ice ? 2 * T : 0);
-  const int CE = 3 * T + J, CO = 4 * T + J;  // first elec / on column (ICE)
-  const int wd = ice ? 4 : 3;                 // entries per demand-charge row
+  const bool ice = g.has_ice != 0, hev = g.has_ev != 0;
+  const int meq = T + 1 + (hev ? T + ev.D : 0);  // the battery's equality rows, then the EV's
+  const int n = (ice || hev ? 5 : 3) * T + J, m = meq + mI + (ice ? 2 * T : 0);
+  const int CE = 3 * T + J, CO = 4 * T + J;  // first elec / on column (ICE), first ev_ch / ev_ene column (EV)
+  const int wd = ice || hev ? 4 : 3;          // entries per demand-charge row
   int32_t* ip = indptr + d[4];
   int32_t* ix = indices + d[5];
   double* dv = data + d[5];
@@ -43,15 +49,17 @@ __global__ __launch_bounds__(kBuildB) void build_battery_kernel(const dvh_batter
   const double E = g.E[w], eta = g.rte[w], sdr = g.sdr[w];
   const double target = g.soc_target[w] * E;
   const int fin = 1 + 4 * (T - 1);  // first entry of the end-of-window row
-  const int dcm0 = fin + 3;         // first entry of the demand-charge rows
+  const int ev0 = fin + 3;          // first entry of the EV rows
+  const int dcm0 = ev0 + (hev ? ev.nnz : 0);  // first entry of the demand-charge rows
   const int ice0 = dcm0 + wd * mI;  // first entry of the ICE rows
   // ---- row pointers
   for (int r = tid; r <= m; r += kBuildB) {
     int v;
     if (r == 0) v = 0;
     else if (r <= T) v = 1 + 4 * (r - 1);
-    else if (r <= T + 1 + mI) v = dcm0 + wd * (r - T - 1);
-    else v = ice0 + 2 * (r - T - 1 - mI);
+    else if (r < meq) continue;  // the EV rows, below
+    else if (r <= meq + mI) v = dcm0 + wd * (r - meq);
+    else v = ice0 + 2 * (r - meq - mI);
     ip[r] = v;
   }
   // ---- entries: row 0 (ene_0 = target), SOE rows (ch_t, dis_t, ene_t, ene_t+1), end row, demand-charge rows
@@ -90,7 +98,55 @@ __global__ __launch_bounds__(kBuildB) void build_battery_kernel(const dvh_batter
       ix[p + 3] = CE + t;
       dv[p + 3] = 1.0;
     }
-    qv[T + 1 + i] = base[t];
+    if (hev) {
+      ix[p + 3] = CE + t;
+      dv[p + 3] = -1.0;
+    }
+    qv[meq + i] = base[t];
+  }
+  if (hev) {  // per step: [ev_ene_t = s], then dt ev_ch_t + ev_ene_t [- ev_ene_{t+1}] = 0 / e
+    const double chm = g.ev_ch_max[w], tgt = g.ev_target[w];
+    const double R = (double)ev.n_trail * dt * chm;
+    const double* da_ = g.has_da ? g.da + (int64_t)w * T : nullptr;
+    const double* rt_ = g.has_retail ? g.retail + (int64_t)w * T : nullptr;
+    for (int t = tid; t < T; t += kBuildB) {
+      const int code = ev.tab[t];
+      int r = ev.tab[T + t], p = ev.tab[2 * T + t];
+      const int st = (code & DVH_EV_START) ? 1 : 0, last = (code & DVH_EV_LAST) ? 1 : 0;
+      // the scanned table against this window's shape: nothing is written outside the EV's rows and entries, and no
+      // column outside the window (a recurrence row on the last step would name ev_ene_T)
+      if (r < T + 1 || r + st >= meq || p < ev0 || p + st + (last ? 2 : 3) > dcm0 || (!last && t + 1 >= T)) continue;
+      if (st) {
+        ip[r] = p;
+        ix[p] = CO + t;
+        dv[p] = 1.0;
+        qv[r] = (code & DVH_EV_START_TARGET) ? tgt : 0.0;
+        ++r;
+        ++p;
+      }
+      ip[r] = p;
+      ix[p] = CE + t;
+      dv[p] = dt;
+      ix[p + 1] = CO + t;
+      dv[p + 1] = 1.0;
+      if (!last) {
+        ix[p + 2] = CO + t + 1;
+        dv[p + 2] = -1.0;
+      }
+      qv[r] = (code & DVH_EV_END_TARGET) ? tgt : (code & DVH_EV_END_R) ? R : 0.0;
+      lv[CE + t] = 0.0;
+      uv[CE + t] = (code & DVH_EV_PLUGGED) ? chm : 0.0;
+      lv[CO + t] = 0.0;
+      uv[CO + t] = (code & DVH_EV_TRAIL) ? R : tgt;
+      // the objective's running sum: the battery's terms add 0 to these columns, then 'ev retailETS', 'ev DA',
+      // 'ev fixed_om'
+      double a = 0.0;
+      if (rt_) a += rt_[t] * dt;
+      if (da_) a += da_[t] * dt;
+      a += 0.0;
+      cv[CE + t] = a;
+      cv[CO + t] = 0.0;
+    }
   }
   if (ice) {  // per step: cap on_t - elec_t >= 0, elec_t - pmin on_t >= 0
     const double cap = g.ice_cap[w], pmin = g.ice_pmin[w];
@@ -104,8 +160,8 @@ __global__ __launch_bounds__(kBuildB) void build_battery_kernel(const dvh_batter
       dv[p + 1] = cap;
       dv[p + 2] = 1.0;
       dv[p + 3] = -pmin;
-      qv[T + 1 + mI + 2 * t] = 0.0;
-      qv[T + 1 + mI + 2 * t + 1] = 0.0;
+      qv[meq + mI + 2 * t] = 0.0;
+      qv[meq + mI + 2 * t + 1] = 0.0;
     }
   }
   // ---- right-hand side of the equality rows
@@ -216,8 +272,9 @@ __global__ __launch_bounds__(kBuildB) void build_battery_kernel(const dvh_batter
 
 }  // namespace
 
-hipError_t launch_build_battery(const dvh_battery_group& g, const dvh_packed& b, int first, hipStream_t s) {
-  hipLaunchKernelGGL(build_battery_kernel, dim3(g.G), dim3(kBuildB), 0, s, g, b.desc, const_cast<int32_t*>(b.indptr),
+hipError_t launch_build_battery(const dvh_battery_group& g, const EvLayout& ev, const dvh_packed& b, int first,
+                                hipStream_t s) {
+  hipLaunchKernelGGL(build_battery_kernel, dim3(g.G), dim3(kBuildB), 0, s, g, ev, b.desc, const_cast<int32_t*>(b.indptr),
                      const_cast<int32_t*>(b.indices), const_cast<double*>(b.data), const_cast<double*>(b.c),
                      const_cast<double*>(b.c0), const_cast<double*>(b.q), const_cast<double*>(b.l),
                      const_cast<double*>(b.u), first);

@@ -62,7 +62,7 @@ DVH_HD inline double neg_inf() { return -__builtin_inf(); }
 DVH_HD inline double max2(double a, double b) { return b > a ? b : a; }
 
 // One window's inputs, the series pointers at its own first step.  x: the window's solution [ch, dis, ene, tau, pv?,
-// elec?, on?], or nullptr when it must not be read (a bad window: original rows only).
+// elec?, on?] or [ch, dis, ene, tau, ev_ch, ev_ene], or nullptr when it must not be read (a bad window: original rows only).
 struct BillIn {
   int T, J, mI;
   double dt;
@@ -76,17 +76,22 @@ struct BillIn {
   const double* demand;  // [J]
   double om, ice_cost;
   const double* x;
+  int has_ev = 0;  // an EV block (ev_ch, ev_ene) after tau; not combined with has_pv / has_ice
   DVH_HD int ipv() const { return 3 * T + J; }
   DVH_HD int ielec() const { return 3 * T + J + (has_pv ? T : 0); }
   // columns the bill reads: a window whose n is below this is bad
-  DVH_HD int64_t need() const { return 3 * (int64_t)T + J + (has_pv ? T : 0) + (has_ice ? 2 * (int64_t)T : 0); }
+  DVH_HD int64_t need() const {
+    return 3 * (int64_t)T + J + (has_pv ? T : 0) + (has_ice ? 2 * (int64_t)T : 0) + (has_ev ? 2 * (int64_t)T : 0);
+  }
 };
 
-// net_t = ((base_t + ch_t) - dis_t) - pv_t - elec_t: adds and subtracts only, in this order (in.x != nullptr)
+// net_t = ((base_t + ch_t) - dis_t) - pv_t - elec_t, or ((base_t + ch_t) - dis_t) + ev_ch_t: adds and subtracts only,
+// in this order (in.x != nullptr)
 DVH_HD inline double net_load(const BillIn& in, int t) {
   double v = (in.base[t] + in.x[t]) - in.x[in.T + t];
   if (in.has_pv) v = v - in.x[in.ipv() + t];
   if (in.has_ice) v = v - in.x[in.ielec() + t];
+  if (in.has_ev) v = v + in.x[in.ipv() + t];
   return v;
 }
 

@@ -97,6 +97,7 @@ struct dvh_handle : dvh_handle_core {
   DevBuf o_data, o_cases, o_len, o_hist, o_soe;  // reliability sweep
   DevBuf s_pairs, s_wts, s_bad;                   // seeded-sweep warm transfer (dvh_sweep.hip)
   DevBuf g_seeds, g_word;                         // scenario series generator (dvh_series.hip)
+  DevBuf g_ev;                                    // device builder: the scanned EV step table (dvh_build_validate.h)
   DevBuf d_route;                                 // cascade lists' counts / ELL widths (dvh_route.hip)
   // certificate pass (dvh_certify.hip): its workspace (allocated on first use) and the device counters
   DevBuf c_tptr, c_tind, c_tval, c_tau, c_gx, c_sig, c_gy, c_counts;

@@ -197,7 +197,13 @@ hipError_t launch_series_draws(const uint64_t* seeds, int count, int steps, int 
                                hipStream_t s);
 hipError_t launch_series_windows(const ::dvh_window_series& w, int32_t* bad, hipStream_t s);
 // Device builder (dvh_build.hip): windows first .. first + g.G - 1 of the packed batch written from the group's series.
-hipError_t launch_build_battery(const ::dvh_battery_group& g, const ::dvh_packed& b, int first, hipStream_t s);
+// tab: device [3T] of a group with has_ev (dvh_build_validate.h EvScan), else unused
+struct EvLayout {
+  const int32_t* tab;
+  int32_t D, nnz, n_trail;
+};
+hipError_t launch_build_battery(const ::dvh_battery_group& g, const EvLayout& ev, const ::dvh_packed& b, int first,
+                                hipStream_t s);
 // Cascade lists on the device (dvh_route.hip): the small windows of [first, first + count) -- or of in_list[0 ..
 // count) -- whose status is `want` (cls 1: and n <= lim_n, m <= lim_m; cls 2: the others; cls 0: any size), in order,
 // to out_list; out_info[0..5] = {their number, max ELL widths wx, wy, max n, m, nnz} over them.

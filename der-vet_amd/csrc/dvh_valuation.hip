@@ -60,6 +60,7 @@ __global__ __launch_bounds__(kBillB) void bill_kernel(const BillArgs a) {
   in.dt = a.g.dt;
   in.has_pv = a.g.has_pv != 0;
   in.has_ice = a.g.has_ice != 0;
+  in.has_ev = a.g.has_ev != 0;
   in.dcm_t = a.g.dcm_t;
   in.dcm_j = a.g.dcm_j;
   in.base = a.g.base + (int64_t)g * T;

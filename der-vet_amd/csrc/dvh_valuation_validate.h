@@ -31,6 +31,7 @@ inline std::string validate_bill_windows(const dvh_bill_group* g, const dvh_pack
   if (g->mI > 0 && (!g->dcm_t || !g->dcm_j)) return "bill: null demand-charge rows";
   if (g->J > 0 && !g->demand) return "bill: null demand prices";
   if (g->has_ice && !g->ice_cost) return "bill: null ICE cost";
+  if (g->has_ev && (g->has_pv || g->has_ice)) return "bill: an EV block is not combined with has_pv / has_ice";
   return "";
 }
 

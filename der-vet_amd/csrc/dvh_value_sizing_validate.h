@@ -22,9 +22,10 @@ inline std::string validate_value_cuts(const dvh_battery_group* g, const dvh_pac
   if ((int64_t)first + g->G > b->count)
     return "value cuts: windows " + std::to_string(first) + " .. " + std::to_string((int64_t)first + g->G - 1) +
            " outside the batch of " + std::to_string(b->count);
-  if (g->has_ice || g->has_emin || g->J > DVH_VALUE_MAX_J) {
+  if (g->has_ice || g->has_ev || g->has_emin || g->J > DVH_VALUE_MAX_J) {
     *code = DVH_ERR_UNSUPPORTED;
     if (g->has_ice) return "value cuts: ICE windows are not sized (has_ice)";
+    if (g->has_ev) return "value cuts: EV windows are not sized (has_ev)";
     if (g->has_emin) return "value cuts: a minimum-SOE series is not supported (has_emin)";
     return "value cuts: J = " + std::to_string(g->J) + " demand-charge columns (at most " +
            std::to_string(DVH_VALUE_MAX_J) + ")";

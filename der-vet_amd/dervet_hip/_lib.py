@@ -94,7 +94,9 @@ class BatteryGroup(ctypes.Structure):
                                                "pch", "pdis", "rte", "sdr", "soc_target", "ulsoc", "llsoc", "om",
                                                "c0")] + \
                [("has_ice", ctypes.c_int32), ("pad_ice", ctypes.c_int32)] + \
-               [(f, ctypes.c_void_p) for f in ("ice_cap", "ice_pmin", "ice_cost")]
+               [(f, ctypes.c_void_p) for f in ("ice_cap", "ice_pmin", "ice_cost")] + \
+               [("has_ev", ctypes.c_int32), ("pad_ev", ctypes.c_int32)] + \
+               [(f, ctypes.c_void_p) for f in ("ev_ch_max", "ev_target", "ev_code")]  # ev_code: a host array
 
 
 
@@ -128,7 +130,8 @@ class BillGroup(ctypes.Structure):
     _fields_ = [("T", ctypes.c_int32), ("J", ctypes.c_int32), ("G", ctypes.c_int32), ("mI", ctypes.c_int32),
                 ("dt", ctypes.c_double), ("has_pv", ctypes.c_int32), ("has_ice", ctypes.c_int32)] + \
                [(f, ctypes.c_void_p) for f in ("dcm_t", "dcm_j", "base", "orig", "retail", "da", "demand", "om",
-                                               "ice_cost")]
+                                               "ice_cost")] + \
+               [("has_ev", ctypes.c_int32), ("pad_ev", ctypes.c_int32)]
 
 
 class ValuationArgs(ctypes.Structure):

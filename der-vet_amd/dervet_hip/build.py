@@ -37,7 +37,7 @@ INCLUDES = {"dvh_band_persist.hip": "dvh_band.hip",  # (a one-line source around
             "dvh_band_persist_ice.hip": "dvh_band.hip"}
 # flags of every object (build() and build_variant()); bench.source_key() hashes them with EXTRA_FLAGS and the compiler
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-result", "-Wno-unused-value"]
-HEADERS = ["dvh_internal.h", "dvh_handle.h", "dvh_host.h", "dvh_device.h", "dvh_validate.h", "dvh_sizing_validate.h", "dvh_rng.h", "dvh_ziggurat.h", "dvh_rainflow.h", "dvh_degradation_validate.h", "dvh_cba.h", "dvh_valuation.h", "dvh_valuation_validate.h", "dvh_value_cut.h", "dvh_value_sizing.h", "dvh_value_sizing_validate.h", os.path.join("..", "..", "include", "dervet_hip.h")]
+HEADERS = ["dvh_internal.h", "dvh_handle.h", "dvh_host.h", "dvh_device.h", "dvh_validate.h", "dvh_sizing_validate.h", "dvh_rng.h", "dvh_ziggurat.h", "dvh_rainflow.h", "dvh_degradation_validate.h", "dvh_cba.h", "dvh_valuation.h", "dvh_valuation_validate.h", "dvh_build_validate.h", "dvh_value_cut.h", "dvh_value_sizing.h", "dvh_value_sizing_validate.h", os.path.join("..", "..", "include", "dervet_hip.h")]
 
 
 def _stale():

@@ -40,6 +40,7 @@ class WindowGroup:
     tags: list = field(default_factory=list)    # per-window identifiers (scenario, window)
     inputs: dict = None     # battery_group: the compact series the bill reads (valuation.BillInputs fields)
     ctrl_load: dict = None  # battery_group with a controllable load: rated_power [G], duration [G], day_starts
+    ev: dict = None         # battery_group with an EV: ch_max, ene_target, fixed_om [G], plugged, code [T]
 
     @property
     def G(self):
@@ -63,7 +64,7 @@ def _col(a, G, T=None):
 
 def battery_group(T, dt, base_load, bat, retail_price=None, da_price=None, demand_masks=None, demand_prices=None,
                   ene_min=None, ene_max=None, name="es", tags=None, pv_curtail_max=None, ice=None, poi=None,
-                  grid_charge=True, pv_gen=None, ctrl_load=None):
+                  grid_charge=True, pv_gen=None, ctrl_load=None, ev=None):
     """Build G windows sharing T steps and the demand masks.
 
     base_load [G, T]  : site load minus fixed generation (kW), hp is added here from ``bat``
@@ -88,6 +89,10 @@ def battery_group(T, dt, base_load, bat, retail_price=None, da_price=None, deman
                       first one 0, shared by the group): a controllable (load-shifting) load, dervet
                       MicrogridDER/LoadControllable.py:215-251 (``_add_ctrl_load``; UNPINNED).  Duration 0 everywhere is
                       a plain load: no block.  Not combined with ice, poi, pv_curtail_max or grid_charge = False.
+    ev                : dict ch_max (kW), ene_target (kWh), fixed_om ($ per window), scalars or [G], and plugged (bool
+                      [T], shared by the group): one electric vehicle, dervet MicrogridDER/ElectricVehicles.py
+                      ElectricVehicle1 (``_add_ev``; UNPINNED).  Not combined with ctrl_load, ice, poi, pv_curtail_max
+                      or grid_charge = False.
     Variable order [ch, dis, ene, tau, pv?, elec?, on?]; >= rows: DCM epigraph, per step the two ICE rows, the POI
     import rows, the POI export rows, the charge-from-PV rows (grid_charge = False with curtailable PV).
     """
@@ -97,6 +102,10 @@ def battery_group(T, dt, base_load, bat, retail_price=None, da_price=None, deman
                                       "pv_curtail_max or grid_charge = False")
     else:
         ctrl_load = None
+    if ev is not None and (ctrl_load is not None or ice is not None or poi is not None or pv_curtail_max is not None
+                           or not grid_charge):
+        raise NotImplementedError("battery_group: an EV is not combined with ctrl_load, ice, poi, pv_curtail_max or "
+                                  "grid_charge = False")
     base_load = np.atleast_2d(np.asarray(base_load, np.float64))
     G = base_load.shape[0]
     masks = np.zeros((0, T), bool) if demand_masks is None else np.asarray(demand_masks, bool)
@@ -269,6 +278,8 @@ def battery_group(T, dt, base_load, bat, retail_price=None, da_price=None, deman
                     q=q, l=l, u=u, terms=terms, tags=list(tags) if tags is not None else [None] * G, inputs=inputs)
     if ctrl_load is not None:
         g = _add_ctrl_load(g, dt, ctrl_load, retail_price, da_price)
+    if ev is not None:
+        g = _add_ev(g, dt, ev, retail_price, da_price)
     return g
 
 
@@ -317,13 +328,28 @@ def _add_ctrl_load(g, dt, ctrl_load, retail_price, da_price):
         l_len.append(2)
         ql[:, r] = EL
         r += 1
+    lo = np.concatenate([-P[:, None] * np.ones((1, T)), np.zeros((G, T))], axis=1)
+    hi = np.concatenate([P[:, None] * np.ones((1, T)), EL[:, None] * np.ones((1, T))], axis=1)
+    extra = [(f"ctrl_load {key}", _col(price, G, T) * dt, np.zeros(G))
+             for key, price in (("DA", da_price), ("retailETS", retail_price)) if price is not None]
+    return _with_load_block(g, l_idx, l_val, l_len, ql, lo, hi, extra, inputs=None,
+                            ctrl_load=dict(rated_power=P, duration=_col(ctrl_load["duration"], G), day_starts=ds))
+
+
+def _with_load_block(g, l_idx, l_val, l_len, ql, lo, hi, extra, **attrs):
+    """The plain battery group ``g`` with two more column blocks [p(T), e(T)] after tau (bounds ``lo`` / ``hi``
+    [G, 2T]), the equality rows given as per-row lists (columns ``l_idx``, values ``l_val``, lengths ``l_len``,
+    right-hand sides ``ql`` [G, rows]) after the battery's T + 1, -p_t as the last entry of every DCM row, and the
+    objective terms ``extra`` (key, coefficients of p [G, T] or None, constant [G]) after the battery's."""
+    G, T, J = g.G, g.T, g.J
+    n0 = g.n
+    ip, n = n0, n0 + 2 * T
     l_idx = np.concatenate([np.asarray(v, np.int64) for v in l_idx])
     l_val = np.concatenate([np.asarray(v, np.float64) for v in l_val])
-    # the DCM rows gain -pw_t (their last column)
     p_eq = int(g.indptr[T + 1])
     mI = g.m - (T + 1)
     dcm_t = g.inputs["dcm_t"].astype(np.int64)
-    d_idx = np.concatenate([g.indices[p_eq:].reshape(mI, 3).astype(np.int64), (ipw + dcm_t)[:, None]], axis=1)
+    d_idx = np.concatenate([g.indices[p_eq:].reshape(mI, 3).astype(np.int64), (ip + dcm_t)[:, None]], axis=1)
     d_val = np.concatenate([g.data[:, p_eq:].reshape(G, mI, 3), np.full((G, mI, 1), -1.0)], axis=2)
     lens = np.concatenate([np.diff(g.indptr[:T + 2]), l_len, np.full(mI, 4)]).astype(np.int64)
     indptr = np.zeros(len(lens) + 1, np.int64)
@@ -331,23 +357,138 @@ def _add_ctrl_load(g, dt, ctrl_load, retail_price, da_price):
     indices = np.concatenate([g.indices[:p_eq].astype(np.int64), l_idx, d_idx.ravel()]).astype(np.int32)
     data = np.concatenate([g.data[:, :p_eq], np.broadcast_to(l_val, (G, len(l_val))), d_val.reshape(G, -1)], axis=1)
     q = np.concatenate([g.q[:, :T + 1], ql, g.q[:, T + 1:]], axis=1)
-    l = np.concatenate([g.l, -P[:, None] * np.ones((1, T)), np.zeros((G, T))], axis=1)
-    u = np.concatenate([g.u, P[:, None] * np.ones((1, T)), EL[:, None] * np.ones((1, T))], axis=1)
+    l = np.concatenate([g.l, lo], axis=1)
+    u = np.concatenate([g.u, hi], axis=1)
     pad = np.zeros((G, 2 * T))
     terms = {k: (np.concatenate([coef, pad], axis=1), const) for k, (coef, const) in g.terms.items()}
-    for key, price in (("DA", da_price), ("retailETS", retail_price)):
-        if price is not None:
-            coef = np.zeros((G, n))
-            coef[:, ipw:ipw + T] = _col(price, G, T) * dt
-            terms[f"ctrl_load {key}"] = (coef, np.zeros(G))
+    for key, cp, const in extra:
+        coef = np.zeros((G, n))
+        if cp is not None:
+            coef[:, ip:ip + T] = cp
+        terms[key] = (coef, const)
     c = np.zeros((G, n))
     c0 = np.zeros(G)
     for coef, const in terms.values():
         c += coef
         c0 += const
-    return WindowGroup(T=T, J=J, m_eq=2 * T + 1 + D, indptr=indptr.astype(np.int32), indices=indices,
-                       data=np.ascontiguousarray(data), c=c, c0=c0, q=q, l=l, u=u, terms=terms, tags=g.tags, inputs=None,
-                       ctrl_load=dict(rated_power=P, duration=_col(ctrl_load["duration"], G), day_starts=ds))
+    return WindowGroup(T=T, J=J, m_eq=T + 1 + len(l_len), indptr=indptr.astype(np.int32), indices=indices,
+                       data=np.ascontiguousarray(data), c=c, c0=c0, q=q, l=l, u=u, terms=terms, tags=g.tags, **attrs)
+
+
+# Per-step codes of an EV block (shared with the device builder, csrc/dvh_build_validate.h): the step's load row is a
+# recurrence (ev_ch_t, ev_ene_t, ev_ene_{t+1}; right-hand side 0) or, on the last step of a cycle, an end row
+# (ev_ch_t, ev_ene_t) whose right-hand side is 0, the target or R; a start row ev_ene_t = 0 or the target precedes it.
+EV_PLUGGED, EV_START, EV_START_TARGET, EV_LAST, EV_END_TARGET, EV_END_R, EV_TRAIL = 1, 2, 4, 8, 16, 32, 64
+
+
+def ev_codes(plugged, T):
+    """int32 [T] step codes of the cycle layout of ``_add_ev`` for a plugged mask (ValueError where the layout, or
+    the reference's own rows, cannot express the mask)."""
+    pl = np.asarray(plugged, bool).ravel()
+    if len(pl) != T:
+        raise ValueError(f"ev plugged: {len(pl)} steps for a window of T = {T}")
+    edges = np.concatenate([[0], np.nonzero(pl[1:] != pl[:-1])[0] + 1, [T]])
+    code = np.zeros(T, np.int32)
+    ended = False
+
+    def cycle(d0, d1, start, end):
+        if start is not None:
+            code[d0] |= EV_START | (EV_START_TARGET if start else 0)
+        code[d1 - 1] |= EV_LAST | end
+
+    for a, b in zip(edges[:-1], edges[1:]):
+        if pl[a]:
+            code[a:b] |= EV_PLUGGED
+            if b < T:
+                cycle(a, b, 0, EV_END_TARGET)
+                ended = True
+            else:  # cut by the window's end: free start, the end row vacuous
+                code[a:b] |= EV_TRAIL
+                cycle(a, b, None, EV_END_R)
+        elif a == 0:
+            cycle(a, b, 0, 0)
+        else:
+            if b == a + 1 and b < T:
+                raise ValueError(f"ev plugged: a one-step unplugged gap at step {a} (the reference's rows pin "
+                                 "ev_ene there to the target and to 0)")
+            cycle(a, a + 1, 1, EV_END_TARGET)
+            if b > a + 1:
+                cycle(a + 1, b, 0, 0)
+    if not ended:
+        raise ValueError("ev plugged: no session ends inside the window")
+    return code
+
+
+def _add_ev(g, dt, ev, retail_price, da_price):
+    """The plain battery group ``g`` with one electric vehicle (dervet MicrogridDER/ElectricVehicles.py:219-297,
+    ElectricVehicle1 in LP mode; uene = uch = 0 left out), laid out in the load-shift form's shape
+    (csrc/dvh_band_shift.hip): every step has one load row, at most one one-entry start row.
+
+      x = [ch, dis, ene, tau, ev_ch(T), ev_ene(T)]
+      bounds           0 <= ev_ch <= ch_max when plugged, ev_ch = 0 when not; 0 <= ev_ene <= ene_target (<= R on a
+                       session cut by the window's end): implied by the rows, the reference's ev_ene is free
+      equality rows after the battery's T + 1, cycle [d0, d1) by cycle in time order
+                       [ev_ene_d0 = s]
+                       dt ev_ch_t + ev_ene_t - ev_ene_{t+1} = 0      t = d0 .. d1 - 2
+                       dt ev_ch_{d1-1} + ev_ene_{d1-1} = e
+      cycles           a session ending at p < T: s = 0, e = ene_target; the unplugged run [p, a') after it: {p} with
+                       s = e = ene_target, then [p + 1, a') with s = e = 0; a leading unplugged run: s = e = 0; a
+                       session [a, T) cut by the window's end: no start row, e = R = (T - a) dt ch_max -- the
+                       reference puts no target on it, and with ev_ene_a free in [0, R] the end row restricts no
+                       ev_ch (the reference's state there is ev_ene_t - ev_ene_a, ``ev_energy``)
+      net load         every DCM row gains -ev_ch_t; 'ev retailETS', 'ev DA' = price_t dt ev_ch_t; 'ev fixed_om'
+                                                                                               (get_charge, :135-144)"""
+    G, T = g.G, g.T
+    code = ev_codes(ev["plugged"], T)
+    chm, tgt, fom = _col(ev["ch_max"], G), _col(ev["ene_target"], G), _col(ev.get("fixed_om", 0.0), G)
+    R = int(np.count_nonzero(code & EV_TRAIL)) * dt * chm
+    iev, iee = g.n, g.n + T
+    l_idx, l_val, l_len = [], [], []
+    D = int(np.count_nonzero(code & EV_START))
+    ql = np.zeros((G, T + D))
+    r = 0
+    for t in range(T):
+        k = int(code[t])
+        if k & EV_START:
+            l_idx.append([iee + t])
+            l_val.append([1.0])
+            l_len.append(1)
+            if k & EV_START_TARGET:
+                ql[:, r] = tgt
+            r += 1
+        if k & EV_LAST:
+            l_idx.append([iev + t, iee + t])
+            l_val.append([dt, 1.0])
+            l_len.append(2)
+            if k & (EV_END_TARGET | EV_END_R):
+                ql[:, r] = tgt if k & EV_END_TARGET else R
+        else:
+            l_idx.append([iev + t, iee + t, iee + t + 1])
+            l_val.append([dt, 1.0, -1.0])
+            l_len.append(3)
+        r += 1
+    plug = (code & EV_PLUGGED) != 0
+    trail = (code & EV_TRAIL) != 0
+    lo = np.zeros((G, 2 * T))
+    hi = np.concatenate([np.where(plug, chm[:, None], 0.0), np.where(trail, R[:, None], tgt[:, None])], axis=1)
+    extra = [(f"ev {key}", _col(price, G, T) * dt, np.zeros(G))
+             for key, price in (("retailETS", retail_price), ("DA", da_price)) if price is not None]
+    extra.append(("ev fixed_om", None, fom))
+    inputs = dict(g.inputs, has_ev=True, ev_ch_max=chm, ev_target=tgt, ev_fixed_om=fom, ev_code=code)
+    return _with_load_block(g, l_idx, l_val, l_len, ql, lo, hi, extra, inputs=inputs,
+                            ev=dict(ch_max=chm, ene_target=tgt, fixed_om=fom, plugged=plug, code=code))
+
+
+def ev_energy(g, x):
+    """The reference's EV state of energy [G, T] of solutions x [G, n] of an EV group: ev_ene, less its free start
+    value on a session cut by the window's end, and zero on unplugged steps other than a plug-out step."""
+    T, code = g.T, g.ev["code"]
+    e = np.array(np.atleast_2d(x)[:, g.n - T:], np.float64)
+    trail = np.nonzero(code & EV_TRAIL)[0]
+    if len(trail):
+        e[:, trail] -= e[:, trail[:1]]
+    e[:, ((code & EV_PLUGGED) == 0) & ((code & EV_START_TARGET) == 0)] = 0.0
+    return e
 
 
 def _assemble(G, m, blocks):

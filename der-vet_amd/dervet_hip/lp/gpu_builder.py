@@ -7,7 +7,8 @@ instead of numpy's.  Values are bit-identical to the host builder (tests/test_gp
 parity reference (tests/test_builder.py pins it to the oracle).
 
 ``battery_group_spec`` takes battery_group's arguments (the supported subset: no curtailable PV, POI rows or
-grid_charge = 0 -- those windows keep the host builder; the LP-relaxed ICE of config 5 is built on the device too) and returns a ``BatteryGroupSpec``; ``pack_specs_device``
+grid_charge = 0 -- those windows keep the host builder; the LP-relaxed ICE of config 5 and the EV block are built on
+the device too) and returns a ``BatteryGroupSpec``; ``pack_specs_device``
 lays a list of specs out as one device PackedBatch (group order, then window order, like ``pack_groups``) and
 builds every window in place.
 """
@@ -18,7 +19,7 @@ import numpy as np
 
 from .. import _lib
 from ..packed import PackedBatch
-from .builder import _col
+from .builder import EV_LAST, EV_START, _col, ev_codes
 
 
 @dataclass
@@ -38,6 +39,7 @@ class BatteryGroupSpec:
     c0: np.ndarray           # [G]
     tags: list = field(default_factory=list)
     ice: dict = None         # LP-relaxed ICE: cap, pmin, cost [G] (battery_group `ice`)
+    ev: dict = None          # one EV: ch_max, ene_target, fixed_om [G], code int32 [T] (battery_group `ev`)
 
     @property
     def G(self):
@@ -45,23 +47,34 @@ class BatteryGroupSpec:
 
     @property
     def n(self):
-        return (5 if self.ice else 3) * self.T + self.J
+        return (5 if self.ice or self.ev else 3) * self.T + self.J
+
+    @property
+    def m_eq(self):
+        return self.T + 1 + (self.T + int(np.count_nonzero(self.ev["code"] & EV_START)) if self.ev else 0)
 
     @property
     def m(self):
-        return self.T + 1 + len(self.dcm_t) + (2 * self.T if self.ice else 0)
+        return self.m_eq + len(self.dcm_t) + (2 * self.T if self.ice else 0)
 
     @property
     def nnz(self):
-        return 4 * self.T + (4 if self.ice else 3) * len(self.dcm_t) + (4 * self.T if self.ice else 0)
+        ev = 0
+        if self.ev:  # per step a start row's entry, and a load row of 3 entries, 2 on a cycle's last step
+            code = self.ev["code"]
+            ev = int(np.count_nonzero(code & EV_START)) + 3 * self.T - int(np.count_nonzero(code & EV_LAST))
+        return 4 * self.T + (4 if self.ice or self.ev else 3) * len(self.dcm_t) + (4 * self.T if self.ice else 0) + ev
 
 
 def battery_group_spec(T, dt, base_load, bat, retail_price=None, da_price=None, demand_masks=None, demand_prices=None,
                        ene_min=None, ene_max=None, name="es", tags=None, pv_curtail_max=None, ice=None, poi=None,
-                       grid_charge=True, pv_gen=None, ctrl_load=None):
+                       grid_charge=True, pv_gen=None, ctrl_load=None, ev=None):
     """The inputs of ``builder.battery_group(...)`` for the device builder (same arguments and meaning)."""
     if ctrl_load is not None and np.any(np.asarray(ctrl_load["duration"], np.float64) != 0.0):
         raise NotImplementedError("device builder: a controllable load uses the host builder")
+    if ev is not None and ice is not None:
+        raise NotImplementedError("battery_group: an EV is not combined with ctrl_load, ice, poi, pv_curtail_max or "
+                                  "grid_charge = False")
     if pv_curtail_max is not None or poi is not None or not grid_charge:
         raise NotImplementedError("device builder: curtailable PV, POI rows and grid_charge = 0 use the host builder")
     base_load = np.atleast_2d(np.asarray(base_load, np.float64))
@@ -95,6 +108,15 @@ def battery_group_spec(T, dt, base_load, bat, retail_price=None, da_price=None, 
     c0 += np.zeros(G)
     if ice is not None:  # the ICE fuel term's constant
         c0 += np.zeros(G)
+    ev_d = None
+    if ev is not None:  # 'ev retailETS', 'ev DA', 'ev fixed_om'
+        ev_d = dict(ch_max=_col(ev["ch_max"], G), ene_target=_col(ev["ene_target"], G),
+                    fixed_om=_col(ev.get("fixed_om", 0.0), G), code=ev_codes(ev["plugged"], T))
+        if retail is not None:
+            c0 += np.zeros(G)
+        if da is not None:
+            c0 += np.zeros(G)
+        c0 += ev_d["fixed_om"]
     scal = dict(E=E, pch=pch, pdis=pdis, rte=_col(bat["rte"], G), sdr=_col(bat.get("sdr", 0.0), G) / 100.0,
                 soc_target=_col(bat.get("soc_target", 1.0), G), ulsoc=_col(bat.get("ulsoc", 1.0), G),
                 llsoc=_col(bat.get("llsoc", 0.0), G), om=_col(bat.get("OMexpenses", 0.0), G))
@@ -109,7 +131,8 @@ def battery_group_spec(T, dt, base_load, bat, retail_price=None, da_price=None, 
                             retail=retail, da=da, demand=demand,
                             emin=None if ene_min is None else np.ascontiguousarray(_col(ene_min, G, T)),
                             emax=None if ene_max is None else np.ascontiguousarray(_col(ene_max, G, T)),
-                            scal=scal, c0=c0, tags=list(tags) if tags is not None else [None] * G, ice=ice_d)
+                            scal=scal, c0=c0, tags=list(tags) if tags is not None else [None] * G, ice=ice_d,
+                            ev=ev_d)
 
 
 def desc_of(specs):
@@ -120,7 +143,7 @@ def desc_of(specs):
     for s in specs:
         G, n, m, nnz = s.G, s.n, s.m, s.nnz
         kk = np.arange(G, dtype=np.int64)
-        desc[k:k + G] = np.stack([np.full(G, n), np.full(G, m), np.full(G, s.T + 1), np.full(G, nnz),
+        desc[k:k + G] = np.stack([np.full(G, n), np.full(G, m), np.full(G, s.m_eq), np.full(G, nnz),
                                   tr + kk * (m + 1), tz + kk * nnz, tn + kk * n, tm + kk * m], axis=1)
         k += G
         tr += G * (m + 1)
@@ -185,6 +208,11 @@ def pack_specs_device(specs, solver, device="cuda:0"):
             g.ice_cap, g.ice_pmin = up(s.ice["cap"]), up(s.ice["pmin"])
             g.ice_cost = up(s.ice["cost"])
             ser["ice_cost"] = held(s.ice["cost"])
+        if s.ev:
+            g.has_ev = 1
+            g.ev_ch_max, g.ev_target = up(s.ev["ch_max"]), up(s.ev["ene_target"])
+            code = np.ascontiguousarray(s.ev["code"], np.int32)  # a host array: the library validates and scans it
+            g.ev_code = code.ctypes.data
         series.append(ser)
         torch.cuda.synchronize(dev)
         rc = solver._lib.dvh_build_battery_group(solver._h, ctypes.byref(g), ctypes.byref(p), first)

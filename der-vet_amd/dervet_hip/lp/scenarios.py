@@ -45,7 +45,7 @@ def tariff(name="data_tariff"):
 def windows_by_period(year, dt, load, gen, bat, tariff_def=None, da_price=None, n="month", ene_min=None,
                       ene_max=None, demand_price_override=None, price_scale=None, tags_prefix=None,
                       pv_curtail_max=None, ice=None, poi=None, grid_charge=True, only=None, spec=False,
-                      ctrl_load=None):
+                      ctrl_load=None, ev=None):
     """Split S scenarios' series [S, Tall] into windows; returns a list of WindowGroup (one per window id).
 
     demand_price_override [S] replaces every demand charge's $/kW (sweep); price_scale [S] scales energy prices.
@@ -54,6 +54,12 @@ def windows_by_period(year, dt, load, gen, bat, tariff_def=None, da_price=None, 
     spec: return the device builder's inputs (gpu_builder.BatteryGroupSpec) instead of host-built groups.
     ctrl_load: dict rated_power, duration (scalars or [S]): a controllable load (builder.battery_group; parity
     unpinned); each window's day_starts are the steps at which the calendar's day of year changes inside it.
+    ev: dict ch_max, ene_target, optional fixed_om (scalars or [S]), plugin_hour, plugout_hour: one electric vehicle
+    (builder.battery_group; parity unpinned); each window's plugged mask is the reference's calendar test (dervet
+    ElectricVehicles.py get_active_times, :203-217): plugged while plugin_hour <= hour < plugout_hour, or around
+    midnight when plugin_hour > plugout_hour.  For dt = 1 h the sessions are the reference's.  For sub-hourly steps the
+    reference also pins the EV's energy to 0 on every step of the plug-in hour (its plug-in test is true for all of
+    them); that quirk is not reproduced: a session starts once, at the hour's first step.
     """
     load = np.atleast_2d(np.asarray(load, np.float64))
     S, Tall = load.shape
@@ -73,6 +79,11 @@ def windows_by_period(year, dt, load, gen, bat, tariff_def=None, da_price=None, 
     else:
         wid = np.arange(Tall) // int(n)
     day = (np.round(np.arange(Tall) * dt * 60.0).astype(np.int64) // 1440) if ctrl_load is not None else None
+    if ev is not None:
+        hour = (np.round(np.arange(Tall) * dt * 60.0).astype(np.int64) // 60) % 24
+        h_in, h_out = int(ev["plugin_hour"]), int(ev["plugout_hour"])
+        plugged = ((hour >= h_in) & (hour < h_out)) if h_in < h_out else \
+            ((hour >= h_in) | (hour < h_out)) if h_in > h_out else np.zeros(Tall, bool)
     groups = []
     for w in np.unique(wid):
         if only is not None and int(w) not in only:
@@ -80,6 +91,9 @@ def windows_by_period(year, dt, load, gen, bat, tariff_def=None, da_price=None, 
         sel = np.nonzero(wid == w)[0]
         T = len(sel)
         extra = {}
+        if ev is not None:
+            extra["ev"] = dict(ch_max=ev["ch_max"], ene_target=ev["ene_target"], fixed_om=ev.get("fixed_om", 0.0),
+                               plugged=plugged[sel])
         if ctrl_load is not None:
             extra["ctrl_load"] = dict(rated_power=ctrl_load["rated_power"], duration=ctrl_load["duration"],
                                       day_starts=np.concatenate([[0], 1 + np.nonzero(np.diff(day[sel]))[0]]))
@@ -211,13 +225,13 @@ def _config4_series(scenarios):
     return P, load, gen
 
 
-def config4(scenarios, n="month", dt=1.0, E=None, only=None, spec=False, ctrl_load=None):
+def config4(scenarios, n="month", dt=1.0, E=None, only=None, spec=False, ctrl_load=None, ev=None):
     """Synthetic sweep windows for the given scenario ids (12 monthly windows each).  n: the optimisation window
     (Model_Parameters_Template_DER.csv:8 `n`: "month", "year" or a step count); dt < 1: sub-hourly steps, the hourly
     series held constant within each hour (Model_Parameters_Template_DER.csv:4 `dt`).  E [S]: the batteries'
     current energy capacity (a degraded battery, dervet_hip.degradation; power ratings stay at the rated E /
     duration); only: window ids to build; spec: the device builder's inputs instead of host-built groups;
-    ctrl_load: as windows_by_period's (``config4_load_shift``)."""
+    ctrl_load, ev: as windows_by_period's (``config4_load_shift``, ``config4_ev``)."""
     P, load, gen = _config4_series(tuple(int(s) for s in scenarios))
     Eb = P["E"] if E is None else np.asarray(E, np.float64)
     bat = dict(E=Eb, Pch=P["E"] / P["duration"], Pdis=P["E"] / P["duration"], rte=P["rte"], sdr=0.0,
@@ -227,13 +241,24 @@ def config4(scenarios, n="month", dt=1.0, E=None, only=None, spec=False, ctrl_lo
         load, gen = np.repeat(load, rep, axis=1), np.repeat(gen, rep, axis=1)
     return windows_by_period(2017, dt, load, gen, bat, tariff_def=tariff(), n=n, demand_price_override=P["demand"],
                              price_scale=P["price_scale"], tags_prefix=list(scenarios), only=only, spec=spec,
-                             **({} if ctrl_load is None else {"ctrl_load": ctrl_load}))
+                             **({} if ctrl_load is None else {"ctrl_load": ctrl_load}),
+                             **({} if ev is None else {"ev": ev}))
 
 
 def config4_load_shift(scenarios, rated_power=150.0, duration=4.0, n="month", only=None):
     """The config-4 population with a controllable (load-shifting) load next to every battery: rated_power (kW) and
     duration (h), scalars or one value per scenario (dervet MicrogridDER/LoadControllable.py; parity unpinned)."""
     return config4(scenarios, n=n, only=only, ctrl_load=dict(rated_power=rated_power, duration=duration))
+
+
+def config4_ev(scenarios, ch_max=50.0, ene_target=200.0, plugin_hour=18, plugout_hour=7, n="month", only=None,
+               spec=False):
+    """The config-4 population with one electric vehicle next to every battery: ch_max (kW) and ene_target (kWh per
+    session), scalars or one value per scenario, plugged from plugin_hour to plugout_hour every day (dervet
+    MicrogridDER/ElectricVehicles.py ElectricVehicle1; parity unpinned; the mask is the reference's for dt = 1 h, see
+    windows_by_period).  spec: the device builder's inputs instead of host-built groups."""
+    return config4(scenarios, n=n, only=only, spec=spec,
+                   ev=dict(ch_max=ch_max, ene_target=ene_target, plugin_hour=plugin_hour, plugout_hour=plugout_hour))
 
 
 def reliability_min_soe(critical_load, hours=4.0, dt=1.0, cap=None):

@@ -206,6 +206,9 @@ def _same_pattern(a, b):
         return False
     if hasattr(a, "indices"):
         return np.array_equal(a.indices, b.indices) and np.array_equal(a.indptr, b.indptr)
+    ea, eb = getattr(a, "ev", None), getattr(b, "ev", None)
+    if (ea is None) != (eb is None) or (ea is not None and not np.array_equal(ea["code"], eb["code"])):
+        return False
     return a.T == b.T and np.array_equal(a.dcm_t, b.dcm_t) and np.array_equal(a.dcm_j, b.dcm_j)
 
 

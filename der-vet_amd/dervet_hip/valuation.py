@@ -83,6 +83,7 @@ class BillInputs:
     ice_cost: object = None  # [G] or None: no ICE block
     has_pv: bool = False    # a curtailable-PV block after tau
     orig: object = None     # [G, T] site load alone, or None: base
+    has_ev: bool = False    # an EV block (ev_ch, ev_ene) after tau; not with has_pv / ice_cost
 
     @property
     def G(self):
@@ -90,7 +91,8 @@ class BillInputs:
 
     @property
     def need(self):
-        return 3 * self.T + self.J + (self.T if self.has_pv else 0) + (2 * self.T if self.ice_cost is not None else 0)
+        return 3 * self.T + self.J + (self.T if self.has_pv else 0) + \
+            (2 * self.T if self.ice_cost is not None else 0) + (2 * self.T if self.has_ev else 0)
 
 
 def bill_inputs(g, orig=None):
@@ -100,13 +102,15 @@ def bill_inputs(g, orig=None):
         return g if orig is None else BillInputs(**{**g.__dict__, "orig": orig})
     if hasattr(g, "scal"):  # BatteryGroupSpec
         return BillInputs(T=g.T, J=g.J, dt=g.dt, dcm_t=g.dcm_t, dcm_j=g.dcm_j, base=g.base, retail=g.retail, da=g.da,
-                          demand=g.demand, om=g.scal["om"], ice_cost=g.ice["cost"] if g.ice else None, orig=orig)
+                          demand=g.demand, om=g.scal["om"], ice_cost=g.ice["cost"] if g.ice else None, orig=orig,
+                          has_ev=g.ev is not None)
     inp = getattr(g, "inputs", None)
     if getattr(g, "ctrl_load", None) is not None:
         raise NotImplementedError("bill: windows with a controllable load are not valued")
     if inp is None:
         raise ValueError("bill: the window group carries no series (builder.battery_group records them in .inputs)")
-    return BillInputs(**inp, orig=orig)
+    # (an EV group's inputs also carry what the device builder reads: ev_ch_max, ev_target, ev_code, ev_fixed_om)
+    return BillInputs(**{k: v for k, v in inp.items() if k in BillInputs.__dataclass_fields__}, orig=orig)
 
 
 # ---- host form of bill_kernel
@@ -161,6 +165,8 @@ def bill_windows_host(inp, x, status=None):
     if has_ice:
         elec = X[:, col:col + T]
         net = net - elec
+    if inp.has_ev:  # the EV's charging is net load
+        net = net + X[:, col:col + T]
     bills = np.zeros((G, BILL_ROWS))
     for price, row, orow in ((inp.retail, RETAIL, ORIG_RETAIL), (inp.da, DA, ORIG_DA)):
         if price is not None:
@@ -415,7 +421,7 @@ def bill_windows(solver, dev, groups_or_specs, orig=None, first=0, peaks=False):
         ser["orig"] = o
         bg = _lib.BillGroup()
         bg.T, bg.J, bg.G, bg.mI, bg.dt = inp.T, inp.J, inp.G, len(inp.dcm_t), inp.dt
-        bg.has_pv, bg.has_ice = int(inp.has_pv), int(inp.ice_cost is not None)
+        bg.has_pv, bg.has_ice, bg.has_ev = int(inp.has_pv), int(inp.ice_cost is not None), int(inp.has_ev)
         for name, t in ser.items():
             setattr(bg, name, None if t is None or t.numel() == 0 else t.data_ptr())
         pk = torch.empty((inp.G, inp.J), dtype=torch.float64, device=device) if peaks else None

@@ -240,7 +240,24 @@ typedef struct dvh_battery_group {
   const double* ice_cap;           /* [G] rated power x units, kW                                                */
   const double* ice_pmin;          /* [G] minimum stable power x units, kW                                       */
   const double* ice_cost;          /* [G] (efficiency x fuel cost + variable O&M) x dt, $/kW per step             */
+  /* One electric vehicle (builder.battery_group `ev`; not with has_ice): columns ev_ch_t, ev_ene_t after tau
+   * (n = 5T + J), -ev_ch_t in every demand-charge row (4 entries), and after the battery's T + 1 equality rows, step by
+   * step, an optional one-entry start row and the step's load row (m_eq = 2T + 1 + D with D start rows, m = m_eq + mI).
+   * ev_code is a HOST array: per step the sum of DVH_EV_* flags.  The library validates it against the descriptors
+   * (DVH_ERR_ARG, nothing launched) and scans it into the rows' offsets.  The reference's own rows and the cycle
+   * layout: dervet_hip/lp/builder.py _add_ev.  dvh_value_cuts refuses has_ev (DVH_ERR_UNSUPPORTED).                  */
+  int32_t has_ev, pad_ev;
+  const double* ev_ch_max;         /* [G] kW                                                                     */
+  const double* ev_target;         /* [G] kWh per session                                                        */
+  const int32_t* ev_code;          /* host [T]                                                                   */
 } dvh_battery_group;
+#define DVH_EV_PLUGGED 1           /* ev_ch_t <= ev_ch_max (else ev_ch_t = 0)                                    */
+#define DVH_EV_START 2             /* a start row ev_ene_t = 0 precedes the step's load row ...                  */
+#define DVH_EV_START_TARGET 4      /* ... its right-hand side is ev_target instead                               */
+#define DVH_EV_LAST 8              /* the last step of a cycle: the load row has no ev_ene_{t+1}, rhs 0 ...      */
+#define DVH_EV_END_TARGET 16       /* ... or ev_target ...                                                       */
+#define DVH_EV_END_R 32            /* ... or R = (steps with DVH_EV_TRAIL) dt ev_ch_max                          */
+#define DVH_EV_TRAIL 64            /* a step of the session cut by the window's end: ev_ene_t <= R               */
 int dvh_build_battery_group(dvh_handle* h, const dvh_battery_group* group, const dvh_packed* batch, int32_t first);
 int dvh_synchronize(dvh_handle* h);
 
@@ -555,6 +572,8 @@ int dvh_degradation_update(dvh_handle* h, const dvh_packed* batch, int32_t first
  * (has_pv: a curtailable-PV block of T columns after tau; has_ice: elec and on after that); the series are the compact
  * arrays of dvh_battery_group (the same device arrays may be passed) plus `orig`, the site load alone.  Per step
  *   net_t = ((base_t + ch_t) - dis_t) - pv_t - elec_t                       (adds and subtracts only, in this order)
+ *   net_t = ((base_t + ch_t) - dis_t) + ev_ch_t                             (has_ev: the EV's charging is net load;
+ *                                                                            the "original" rows are unchanged)
  * and bills[g][0 .. DVH_BILL_ROWS - 1] =
  *   [0] retail energy charge  sum_t (retail_t dt) net_t              [5] the same of orig_t (the golden "Original")
  *   [1] demand charge  sum_j demand_j max_{rows i, dcm_j[i] = j} net_{dcm_t[i]}, in j order   [6] the same of orig
@@ -580,6 +599,7 @@ typedef struct dvh_bill_group {
   const double* demand;            /* [G*J] $/kW                                                                 */
   const double* om;                /* [G] variable O&M, $/MWh, or NULL: 0                                        */
   const double* ice_cost;          /* [G] $/kW per step (dvh_battery_group ice_cost); has_ice                    */
+  int32_t has_ev, pad_ev;          /* an EV block (ev_ch, ev_ene: 2T columns) after tau; not with has_pv / has_ice  */
 } dvh_bill_group;
 int dvh_bill_windows(dvh_handle* h, const dvh_bill_group* group, const dvh_packed* batch, int32_t first,
                      double* bills, double* peaks, int32_t* bad, void* stream);
