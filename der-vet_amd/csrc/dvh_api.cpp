@@ -257,7 +257,7 @@ int dvh_set_launch_order(dvh_handle* h, const int32_t* order, int32_t count) {
 }
 
 int dvh_set_kernel_path(dvh_handle* h, int mode) {
-  if (!h || mode < 0 || mode > 6) return DVH_ERR_ARG;
+  if (!h || mode < 0 || mode > 7) return DVH_ERR_ARG;
   h->kernel_path = mode;
   for (dvh_handle* p : h->peers) p->kernel_path = mode;
   return DVH_OK;

@@ -158,7 +158,8 @@ int chain_pass(dvh_handle* h, const dvh::Batch& b, const dvh::Work& w, const dvh
 // rest), each instantiation sized for its class -> what they refuse (-1) or cannot hold through the generic CSR
 // kernel, both classes in one launch.  With dvh_set_kernel_path 5 the band kernel's interconnection form (POI limit
 // rows, curtailable PV, charge-from-PV rows) runs over the ICE pass's list right behind it; with 6 the load-shift form
-// (controllable-load windows, dvh_band_shift.hip) does, in the same place.
+// (controllable-load windows, dvh_band_shift.hip) does, in the same place; with 7 the heat form (windows with a
+// combined-heat-and-power unit, dvh_band_heat.hip).
 // One small read-back per stage that ran ({count, ELL widths, max n / m / nnz} of the windows it hands on; two after
 // the ICE form when it refuses windows: their count, then their size classes once they are set up); a batch the band
 // kernel takes whole waits once.
@@ -230,6 +231,8 @@ int device_cascade(dvh_handle* h, const dvh::Batch& b, const dvh::Work& w, const
     if (h->kernel_path == 5) DVH_HIP(h, dvh::launch_pdhg_band_grid(b, w, ch, o, s, L[0], cur, &bvar, early_counters(h)));
     // dvh_set_kernel_path 6: the load-shift form (dvh_band_shift.hip), launched the same way
     if (h->kernel_path == 6) DVH_HIP(h, dvh::launch_pdhg_band_shift(b, w, ch, o, s, L[0], cur, &bvar));
+    // dvh_set_kernel_path 7: the heat form (dvh_band_heat.hip: windows with a combined-heat-and-power unit), likewise
+    if (h->kernel_path == 7) DVH_HIP(h, dvh::launch_pdhg_band_heat(b, w, ch, o, s, L[0], cur, &bvar));
     DVH_HIP(h, route(1, L[0], cur, -2, 0, 4));
     if (box_ice) DVH_HIP(h, route(2, L[0], cur, -3, 0, 1));
     DVH_HIP(h, readback(1, box_ice ? 2 : 1));

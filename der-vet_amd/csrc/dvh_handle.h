@@ -112,11 +112,16 @@ struct dvh_handle : dvh_handle_core {
   int last_band_variant = -1;  // the battery band pass's instantiation code (dvh_last_band_variant), -1: it took nothing
   int kernel_path = 0;  // 0 band -> ELL -> generic, 1 generic only, 2 ELL -> generic (no band kernel), 3 / 4 as 0
                         // with the battery band kernel's one-step / three-step form forced (0 picks by batch size),
-                        // 5 as 0 plus the band kernel's interconnection form, 6 as 0 plus its load-shift form
+                        // 5 as 0 plus the band kernel's interconnection form, 6 as 0 plus its load-shift form,
+                        // 7 as 0 plus its heat form
   int cus = 0;          // compute units of the device (band kernel form choice)
   std::vector<int32_t> order;  // dvh_set_launch_order: the next solve's band-pass window order (empty: packing order)
   std::vector<int32_t> order_used;  // (the copy a solve consumed: kept until the next one, the H2D copy reads it)
   DevBuf d_order;
+  // kernel path 7: the heat-sized windows above dvh::kSmallMax, which the heat form examines before the grid-wide path
+  // (solve_packed); the host copy is kept until the next solve, the H2D copy reads it
+  std::vector<int32_t> heat_list;
+  DevBuf d_heat_list;
   // Further devices of this handle (device_mask bits after the first, or dvh_create_devices): same options; a
   // host-buffer batch is split into contiguous, cost-balanced ranges, one per device, solved concurrently (one host
   // thread per device, no inter-device traffic), results written straight into the caller's buffers.

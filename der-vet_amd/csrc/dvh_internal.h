@@ -311,6 +311,18 @@ hipError_t launch_pdhg_band_grid(const Batch& b, const Work& w, const Chunk& ch,
 hipError_t launch_pdhg_band_shift(const Batch& b, const Work& w, const Chunk& ch, const Opts& o, hipStream_t s,
                                   const int32_t* list, int nlist, int* variant_out);
 
+// The band kernel's heat form (dvh_band_heat.hip; dvh_set_kernel_path 7): battery windows with one combined-heat-and-power
+// unit (four more column blocks elec, on, steam, hotwater; T heat rows after the battery's T + 1; per step two generator
+// rows and one ratio row among the >= rows), one workgroup per listed window.  gate: as the load-shift form, a workgroup
+// returns at once unless its window's status is -2 (kNeedsEll), so the launch follows the ICE pass over the same list;
+// without it every listed window is examined (solve_packed's launch over the heat-sized windows above kSmallMax).
+// Windows it refuses have status -2.  variant_out: 9000000 + 400 + waves per window.
+hipError_t launch_pdhg_band_heat(const Batch& b, const Work& w, const Chunk& ch, const Opts& o, hipStream_t s,
+                                 const int32_t* list, int nlist, int* variant_out, bool gate = true);
+// The descriptor's sizes are those of a window the heat form can hold (m_eq = 2 T + 1, T <= 768, n = 7 T + J, J <= 4,
+// 3 T .. 4 T >= rows): its largest windows are above kSmallMax (n = 5,380, m = 4,609).
+bool band_heat_sized(int64_t n, int64_t m, int64_t meq);
+
 // Certificate pass (dvh_certify.hip; dvh_options.certify, dvh_certify_batch): plain PDHG on the unscaled LP of every
 // on-chip window of the batch, one workgroup each, until a Farkas certificate (status 1, the ray in y) or an unbounded
 // ray (status 2, the ray in x) passes its test or `cap` iterations are done.  gate != 0 (after a solve): a workgroup

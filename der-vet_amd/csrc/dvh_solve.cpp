@@ -310,8 +310,31 @@ int solve_packed(dvh_handle* h, const dvh_packed* bt, const std::vector<int64_t>
     order = h->d_order.as<int32_t>();
   }
   std::vector<char> med_done(count, 0);  // solved (or reported infeasible) by the medium tier
-  for (const ChunkPlan& c : plan.chunks) {
-    if (c.nsmall == 0 && c.med.empty()) continue;
+  // dvh_set_kernel_path 7: the heat form holds windows above kSmallMax (T = 768: n = 5,380, m = 4,609), which no chunk
+  // counts among its small windows.  Those of its size (by the descriptor) are listed per chunk and examined by the form
+  // behind the chunk's tiers; what it refuses (status -2) stays with the grid-wide path below.  One status read-back
+  // for the whole batch, only when such windows exist.
+  std::vector<int> heat_first(plan.chunks.size() + 1, 0);
+  h->heat_list.clear();
+  if (cascade && h->kernel_path == 7) {
+    for (size_t ci = 0; ci < plan.chunks.size(); ++ci) {
+      const dvh::Chunk& ch = plan.chunks[ci].ch;
+      for (int k = ch.first; k < ch.first + ch.count; ++k) {
+        const int64_t* d = &desc[8 * (size_t)k];
+        if (is_large(d) && dvh::band_heat_sized(d[0], d[1], d[2])) h->heat_list.push_back(k);
+      }
+      heat_first[ci + 1] = (int)h->heat_list.size();
+    }
+    if (!h->heat_list.empty()) {
+      DVH_HIP(h, h->d_heat_list.ensure(I * h->heat_list.size()));
+      DVH_HIP(h, hipMemcpyAsync(h->d_heat_list.p, h->heat_list.data(), I * h->heat_list.size(), hipMemcpyHostToDevice, s));
+    }
+  }
+  int heat_variant = -1;
+  for (size_t ci = 0; ci < plan.chunks.size(); ++ci) {
+    const ChunkPlan& c = plan.chunks[ci];
+    const int nheat = heat_first[ci + 1] - heat_first[ci];
+    if (c.nsmall == 0 && c.med.empty() && nheat == 0) continue;
     const DevEvent* ce = nullptr;
     if (int rc = next_chunk_events(h, ce)) return rc;
     DVH_HIP(h, hipEventRecord(ce[0], s));
@@ -323,7 +346,23 @@ int solve_packed(dvh_handle* h, const dvh_packed* bt, const std::vector<int64_t>
                            : host_list_tiers(h, b, w, c, o, fast, desc, s))
         return rc;
     if (int rc = dvh::chain_pass(h, b, w, c.ch, o, c.med, c.med_T, desc, med_done, s)) return rc;
+    if (nheat > 0)
+      DVH_HIP(h, dvh::launch_pdhg_band_heat(b, w, c.ch, o, s, h->d_heat_list.as<int32_t>() + heat_first[ci], nheat,
+                                            &heat_variant, false));
     DVH_HIP(h, hipEventRecord(ce[2], s));
+  }
+  if (!h->heat_list.empty()) {  // which of them the form took: the others go on to the grid-wide path
+    std::vector<int32_t> ist(2 * (size_t)count);
+    DVH_HIP(h, hipMemcpyAsync(ist.data(), b.istats, I * ist.size(), hipMemcpyDeviceToHost, s));
+    DVH_HIP(h, sync_stream(h, s));
+    int took = 0;
+    for (int k : h->heat_list)
+      if (ist[2 * (size_t)k] != -2) {  // (-2: the band kernels' "not mine")
+        med_done[k] = 1;
+        ++took;
+      }
+    h->st.n_band += took;
+    if (took > 0 && (h->last_variant < 0 || took == count)) h->last_variant = heat_variant;
   }
   // windows above the on-chip limits that the medium tier did not take: one at a time, the whole GPU each
   for (int k : plan.large) {

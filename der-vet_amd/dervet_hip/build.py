@@ -15,7 +15,7 @@ LIB = os.path.join(HERE, "libdervet_hip.so")
 # its PMC profiles to it without running hipcc from a process that may already hold the GPU (under rocprofv3 --pmc it
 # does, and the GPU box refuses an exec from such a process)
 BUILDINFO = os.path.join(HERE, "libdervet_hip.buildinfo.json")
-SOURCES = ["dvh_kernels.hip", "dvh_band.hip", "dvh_band_persist.hip", "dvh_band_persist_ice.hip", "dvh_band_grid.hip", "dvh_band_shift.hip", "dvh_chain.hip", "dvh_build.hip", "dvh_sweep.hip", "dvh_series.hip", "dvh_route.hip", "dvh_large.hip", "dvh_outage.hip",
+SOURCES = ["dvh_kernels.hip", "dvh_band.hip", "dvh_band_persist.hip", "dvh_band_persist_ice.hip", "dvh_band_grid.hip", "dvh_band_shift.hip", "dvh_band_heat.hip", "dvh_chain.hip", "dvh_build.hip", "dvh_sweep.hip", "dvh_series.hip", "dvh_route.hip", "dvh_large.hip", "dvh_outage.hip",
            "dvh_certify.hip", "dvh_sizing.hip", "dvh_degradation.hip", "dvh_valuation.hip", "dvh_value_sizing.hip", "dvh_api.cpp", "dvh_api_outage.cpp", "dvh_api_build.cpp",
            "dvh_api_valuation.cpp", "dvh_api_value_sizing.cpp", "dvh_solve.cpp",
            "dvh_cascade.cpp", "dvh_validate.cpp", "dvh_comm.cpp", "dvh_sizing.cpp", "dvh_sizing_validate.cpp"]

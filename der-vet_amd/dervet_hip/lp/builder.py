@@ -41,6 +41,8 @@ class WindowGroup:
     inputs: dict = None     # battery_group: the compact series the bill reads (valuation.BillInputs fields)
     ctrl_load: dict = None  # battery_group with a controllable load: rated_power [G], duration [G], day_starts
     ev: dict = None         # battery_group with an EV: ch_max, ene_target, fixed_om [G], plugged, code [T]
+    chp: dict = None        # battery_group with a CHP: cap, pmin, electric_heat_ratio, max_steam_ratio, variable_om_cost,
+                            # fixed_om [G], fuel_price, steam_load, hotwater_load [G, T]
 
     @property
     def G(self):
@@ -64,7 +66,7 @@ def _col(a, G, T=None):
 
 def battery_group(T, dt, base_load, bat, retail_price=None, da_price=None, demand_masks=None, demand_prices=None,
                   ene_min=None, ene_max=None, name="es", tags=None, pv_curtail_max=None, ice=None, poi=None,
-                  grid_charge=True, pv_gen=None, ctrl_load=None, ev=None):
+                  grid_charge=True, pv_gen=None, ctrl_load=None, ev=None, chp=None):
     """Build G windows sharing T steps and the demand masks.
 
     base_load [G, T]  : site load minus fixed generation (kW), hp is added here from ``bat``
@@ -93,6 +95,12 @@ def battery_group(T, dt, base_load, bat, retail_price=None, da_price=None, deman
                       [T], shared by the group): one electric vehicle, dervet MicrogridDER/ElectricVehicles.py
                       ElectricVehicle1 (``_add_ev``; UNPINNED).  Not combined with ctrl_load, ice, poi, pv_curtail_max
                       or grid_charge = False.
+    chp               : dict rated_power (kW), n, min_power (kW), electric_heat_ratio, max_steam_ratio, variable_om_cost
+                      ($/kWh), fixed_om ($ per window), scalars or [G], and fuel_price ($ per kWh of electricity),
+                      steam_load, hotwater_load (in the unit of the steam / hotwater columns; a missing load is zeros),
+                      [G, T] or [T]: one combined-heat-and-power unit with the site's thermal loads, dervet
+                      MicrogridDER/CombinedHeatPower.py (``_add_chp``; UNPINNED; the commitment LP-relaxed as ice's).
+                      Not combined with ice, poi, pv_curtail_max, grid_charge = False, ctrl_load or ev.
     Variable order [ch, dis, ene, tau, pv?, elec?, on?]; >= rows: DCM epigraph, per step the two ICE rows, the POI
     import rows, the POI export rows, the charge-from-PV rows (grid_charge = False with curtailable PV).
     """
@@ -106,6 +114,10 @@ def battery_group(T, dt, base_load, bat, retail_price=None, da_price=None, deman
                            or not grid_charge):
         raise NotImplementedError("battery_group: an EV is not combined with ctrl_load, ice, poi, pv_curtail_max or "
                                   "grid_charge = False")
+    if chp is not None and (ctrl_load is not None or ev is not None or ice is not None or poi is not None
+                            or pv_curtail_max is not None or not grid_charge):
+        raise NotImplementedError("battery_group: a CHP is not combined with ice, poi, pv_curtail_max, "
+                                  "grid_charge = False, ctrl_load or ev")
     base_load = np.atleast_2d(np.asarray(base_load, np.float64))
     G = base_load.shape[0]
     masks = np.zeros((0, T), bool) if demand_masks is None else np.asarray(demand_masks, bool)
@@ -280,6 +292,8 @@ def battery_group(T, dt, base_load, bat, retail_price=None, da_price=None, deman
         g = _add_ctrl_load(g, dt, ctrl_load, retail_price, da_price)
     if ev is not None:
         g = _add_ev(g, dt, ev, retail_price, da_price)
+    if chp is not None:
+        g = _add_chp(g, dt, chp, retail_price, da_price)
     return g
 
 
@@ -477,6 +491,85 @@ def _add_ev(g, dt, ev, retail_price, da_price):
     inputs = dict(g.inputs, has_ev=True, ev_ch_max=chm, ev_target=tgt, ev_fixed_om=fom, ev_code=code)
     return _with_load_block(g, l_idx, l_val, l_len, ql, lo, hi, extra, inputs=inputs,
                             ev=dict(ch_max=chm, ene_target=tgt, fixed_om=fom, plugged=plug, code=code))
+
+
+def _add_chp(g, dt, chp, retail_price, da_price):
+    """The plain battery group ``g`` with one combined-heat-and-power unit (dervet MicrogridDER/CombinedHeatPower.py:85-97
+    on CombustionTurbine.py / RotatingGeneratorSizing.py:110-136, and the site's thermal balance, MicrogridPOI.py:215-258),
+    the ``on`` commitment relaxed to [0, 1] as ``ice=`` does, laid out in the heat form's shape (csrc/dvh_band_heat.hip).
+    With cap = rated_power x n, pmin = min_power x n, ehr = electric_heat_ratio, ratio = max_steam_ratio:
+
+      x = [ch, dis, ene, tau, elec(T), on(T), steam(T), hotwater(T)]
+      bounds           0 <= elec, 0 <= on <= 1, steam_t >= steam_load_t, hotwater_t >= hotwater_load_t (no upper bound):
+                       the POI's rows -steam_in + site_steam_load <= 0 (MicrogridPOI.py:245-252) with one hot DER, whose
+                       steam is steam_in
+      equality rows after the battery's T + 1
+                       -elec_t + ehr steam_t + ehr hotwater_t = 0                              (CombinedHeatPower.py:95)
+      >= rows after the DCM rows, step by step
+                       -elec_t + cap on_t >= 0,  elec_t - pmin on_t >= 0         (RotatingGeneratorSizing.py:110-136)
+                       -steam_t + ratio hotwater_t >= 0                                        (CombinedHeatPower.py:93)
+      net load         every DCM row gains +elec_t; the retail / DA terms gain -price_t dt elec_t (as ``ice=``)
+      objective keys   'chp naturalgas_fuel_cost' = fuel_price_t dt elec_t (CombustionTurbine.py:79-88), 'chp variable_om'
+                       = variable_om_cost dt elec_t, 'chp fixed_om' (a constant, $ per window)
+
+    Units: fuel_price is $ per kWh of electricity (the caller forms heat rate x gas price; neither the reference's 1e6 on
+    a $/MMBTU price in the objective, CombustionTurbine.py:85-86, nor its absence in the pro forma, :144, is restated);
+    the thermal loads are in the unit of the steam / hotwater columns (the reference compares its BTU/hr series to them
+    directly).  A missing load is zeros (DERVETParams.py:616-627).
+
+    The group carries no ``inputs``: valuation, the device builder and economic sizing do not take these windows."""
+    G, T, J = g.G, g.T, g.J
+    nn = _col(chp.get("n", 1.0), G)
+    cap, pmin = _col(chp["rated_power"], G) * nn, _col(chp.get("min_power", 0.0), G) * nn
+    ehr, ratio = _col(chp["electric_heat_ratio"], G), _col(chp["max_steam_ratio"], G)
+    vom, fom = _col(chp.get("variable_om_cost", 0.0), G), _col(chp.get("fixed_om", 0.0), G)
+    fuel = _col(chp["fuel_price"], G, T)
+    sload = np.zeros((G, T)) if chp.get("steam_load") is None else _col(chp["steam_load"], G, T)
+    hload = np.zeros((G, T)) if chp.get("hotwater_load") is None else _col(chp["hotwater_load"], G, T)
+    n0 = g.n
+    iel, ion, ist, ihw, n = n0, n0 + T, n0 + 2 * T, n0 + 3 * T, n0 + 4 * T
+    t = np.arange(T, dtype=np.int64)
+    p_eq = int(g.indptr[T + 1])
+    mI = g.m - (T + 1)
+    dcm_t = g.inputs["dcm_t"].astype(np.int64)
+    one = np.ones((G, T))
+    # heat rows (sorted columns: elec_t < steam_t < hotwater_t)
+    h_idx = np.stack([iel + t, ist + t, ihw + t], axis=1)
+    h_val = np.stack([-one, ehr[:, None] * one, ehr[:, None] * one], axis=2)
+    # DCM rows with +elec_t as their last entry
+    d_idx = np.concatenate([g.indices[p_eq:].reshape(mI, 3).astype(np.int64), (iel + dcm_t)[:, None]], axis=1)
+    d_val = np.concatenate([g.data[:, p_eq:].reshape(G, mI, 3), np.ones((G, mI, 1))], axis=2)
+    # per step: cap row (elec_t, on_t), min row (elec_t, on_t), ratio row (steam_t, hotwater_t)
+    s_idx = np.stack([iel + t, ion + t, iel + t, ion + t, ist + t, ihw + t], axis=1)
+    s_val = np.stack([-one, cap[:, None] * one, one, -pmin[:, None] * one, -one, ratio[:, None] * one], axis=2)
+    lens = np.concatenate([np.diff(g.indptr[:T + 2]), np.full(T, 3), np.full(mI, 4), np.full(3 * T, 2)]).astype(np.int64)
+    indptr = np.zeros(len(lens) + 1, np.int64)
+    np.cumsum(lens, out=indptr[1:])
+    indices = np.concatenate([g.indices[:p_eq].astype(np.int64), h_idx.ravel(), d_idx.ravel(), s_idx.ravel()]).astype(np.int32)
+    data = np.concatenate([g.data[:, :p_eq], h_val.reshape(G, -1), d_val.reshape(G, -1), s_val.reshape(G, -1)], axis=1)
+    q = np.concatenate([g.q[:, :T + 1], np.zeros((G, T)), g.q[:, T + 1:], np.zeros((G, 3 * T))], axis=1)
+    l = np.concatenate([g.l, np.zeros((G, 2 * T)), sload, hload], axis=1)
+    u = np.concatenate([g.u, np.full((G, T), np.inf), np.ones((G, T)), np.full((G, 2 * T), np.inf)], axis=1)
+    pad = np.zeros((G, 4 * T))
+    terms = {k: (np.concatenate([coef, pad], axis=1), const) for k, (coef, const) in g.terms.items()}
+    for key, price in (("DA", da_price), ("retailETS", retail_price)):
+        if price is not None:
+            terms[key][0][:, iel:iel + T] = -_col(price, G, T) * dt
+    for key, cp, const in (("chp naturalgas_fuel_cost", fuel * dt, np.zeros(G)),
+                           ("chp variable_om", (vom * dt)[:, None] * one, np.zeros(G)), ("chp fixed_om", None, fom)):
+        coef = np.zeros((G, n))
+        if cp is not None:
+            coef[:, iel:iel + T] = cp
+        terms[key] = (coef, const)
+    c = np.zeros((G, n))
+    c0 = np.zeros(G)
+    for coef, const in terms.values():
+        c += coef
+        c0 += const
+    return WindowGroup(T=T, J=J, m_eq=2 * T + 1, indptr=indptr.astype(np.int32), indices=indices,
+                       data=np.ascontiguousarray(data), c=c, c0=c0, q=q, l=l, u=u, terms=terms, tags=g.tags, inputs=None,
+                       chp=dict(cap=cap, pmin=pmin, electric_heat_ratio=ehr, max_steam_ratio=ratio, variable_om_cost=vom,
+                                fixed_om=fom, fuel_price=fuel, steam_load=sload, hotwater_load=hload))
 
 
 def ev_energy(g, x):

@@ -68,8 +68,10 @@ class BatteryGroupSpec:
 
 def battery_group_spec(T, dt, base_load, bat, retail_price=None, da_price=None, demand_masks=None, demand_prices=None,
                        ene_min=None, ene_max=None, name="es", tags=None, pv_curtail_max=None, ice=None, poi=None,
-                       grid_charge=True, pv_gen=None, ctrl_load=None, ev=None):
+                       grid_charge=True, pv_gen=None, ctrl_load=None, ev=None, chp=None):
     """The inputs of ``builder.battery_group(...)`` for the device builder (same arguments and meaning)."""
+    if chp is not None:
+        raise NotImplementedError("device builder: a CHP uses the host builder")
     if ctrl_load is not None and np.any(np.asarray(ctrl_load["duration"], np.float64) != 0.0):
         raise NotImplementedError("device builder: a controllable load uses the host builder")
     if ev is not None and ice is not None:

@@ -45,7 +45,7 @@ def tariff(name="data_tariff"):
 def windows_by_period(year, dt, load, gen, bat, tariff_def=None, da_price=None, n="month", ene_min=None,
                       ene_max=None, demand_price_override=None, price_scale=None, tags_prefix=None,
                       pv_curtail_max=None, ice=None, poi=None, grid_charge=True, only=None, spec=False,
-                      ctrl_load=None, ev=None):
+                      ctrl_load=None, ev=None, chp=None):
     """Split S scenarios' series [S, Tall] into windows; returns a list of WindowGroup (one per window id).
 
     demand_price_override [S] replaces every demand charge's $/kW (sweep); price_scale [S] scales energy prices.
@@ -60,6 +60,8 @@ def windows_by_period(year, dt, load, gen, bat, tariff_def=None, da_price=None, 
     midnight when plugin_hour > plugout_hour.  For dt = 1 h the sessions are the reference's.  For sub-hourly steps the
     reference also pins the EV's energy to 0 on every step of the plug-in hour (its plug-in test is true for all of
     them); that quirk is not reproduced: a session starts once, at the hour's first step.
+    chp: dict as builder.battery_group's (parity unpinned), its scalars per scenario ([S]) or shared, its series
+    fuel_price, steam_load, hotwater_load [S, Tall] or [Tall] (a missing load is zeros), cut into the windows.
     """
     load = np.atleast_2d(np.asarray(load, np.float64))
     S, Tall = load.shape
@@ -94,6 +96,9 @@ def windows_by_period(year, dt, load, gen, bat, tariff_def=None, da_price=None, 
         if ev is not None:
             extra["ev"] = dict(ch_max=ev["ch_max"], ene_target=ev["ene_target"], fixed_om=ev.get("fixed_om", 0.0),
                                plugged=plugged[sel])
+        if chp is not None:
+            extra["chp"] = {k: (v if k not in ("fuel_price", "steam_load", "hotwater_load") or v is None or np.ndim(v) == 0
+                                else np.asarray(v, np.float64)[..., sel]) for k, v in chp.items()}
         if ctrl_load is not None:
             extra["ctrl_load"] = dict(rated_power=ctrl_load["rated_power"], duration=ctrl_load["duration"],
                                       day_starts=np.concatenate([[0], 1 + np.nonzero(np.diff(day[sel]))[0]]))
@@ -225,13 +230,13 @@ def _config4_series(scenarios):
     return P, load, gen
 
 
-def config4(scenarios, n="month", dt=1.0, E=None, only=None, spec=False, ctrl_load=None, ev=None):
+def config4(scenarios, n="month", dt=1.0, E=None, only=None, spec=False, ctrl_load=None, ev=None, chp=None):
     """Synthetic sweep windows for the given scenario ids (12 monthly windows each).  n: the optimisation window
     (Model_Parameters_Template_DER.csv:8 `n`: "month", "year" or a step count); dt < 1: sub-hourly steps, the hourly
     series held constant within each hour (Model_Parameters_Template_DER.csv:4 `dt`).  E [S]: the batteries'
     current energy capacity (a degraded battery, dervet_hip.degradation; power ratings stay at the rated E /
     duration); only: window ids to build; spec: the device builder's inputs instead of host-built groups;
-    ctrl_load, ev: as windows_by_period's (``config4_load_shift``, ``config4_ev``)."""
+    ctrl_load, ev, chp: as windows_by_period's (``config4_load_shift``, ``config4_ev``, ``config4_chp``)."""
     P, load, gen = _config4_series(tuple(int(s) for s in scenarios))
     Eb = P["E"] if E is None else np.asarray(E, np.float64)
     bat = dict(E=Eb, Pch=P["E"] / P["duration"], Pdis=P["E"] / P["duration"], rte=P["rte"], sdr=0.0,
@@ -242,7 +247,7 @@ def config4(scenarios, n="month", dt=1.0, E=None, only=None, spec=False, ctrl_lo
     return windows_by_period(2017, dt, load, gen, bat, tariff_def=tariff(), n=n, demand_price_override=P["demand"],
                              price_scale=P["price_scale"], tags_prefix=list(scenarios), only=only, spec=spec,
                              **({} if ctrl_load is None else {"ctrl_load": ctrl_load}),
-                             **({} if ev is None else {"ev": ev}))
+                             **({} if ev is None else {"ev": ev}), **({} if chp is None else {"chp": chp}))
 
 
 def config4_load_shift(scenarios, rated_power=150.0, duration=4.0, n="month", only=None):
@@ -259,6 +264,27 @@ def config4_ev(scenarios, ch_max=50.0, ene_target=200.0, plugin_hour=18, plugout
     windows_by_period).  spec: the device builder's inputs instead of host-built groups."""
     return config4(scenarios, n=n, only=only, spec=spec,
                    ev=dict(ch_max=ch_max, ene_target=ene_target, plugin_hour=plugin_hour, plugout_hour=plugout_hour))
+
+
+def config4_chp(scenarios, rated_power=300.0, min_power=60.0, electric_heat_ratio=0.8, max_steam_ratio=1.5,
+                variable_om_cost=0.005, fixed_om=0.0, fuel_price=0.08, steam_load=80.0, hotwater_load=90.0, n="month",
+                only=None):
+    """The config-4 population with one combined-heat-and-power unit next to every battery (dervet
+    MicrogridDER/CombinedHeatPower.py; parity unpinned): the unit's scalars, one value per scenario or shared, and the
+    site's series laid on the 2017 calendar as ``config4_ev`` lays its sessions, from three levels: steam_load in full
+    from 8 h to 18 h and at 40 % otherwise, hotwater_load in full from 6 h to 9 h and from 17 h to 21 h and at half
+    otherwise, fuel_price ($ per kWh of electricity) a quarter higher from December to February.  The levels' defaults
+    keep the thermal must-run, electric_heat_ratio x (steam + max(hotwater, steam / max_steam_ratio)), at 136 kW at most,
+    below the 300 kW unit."""
+    month, he, _, _ = _tariff.calendar(2017, 8760, 1.0)
+    hour = (np.asarray(he, np.int64) - 1) % 24
+    steam = float(steam_load) * np.where((hour >= 8) & (hour < 18), 1.0, 0.4)
+    hot = float(hotwater_load) * np.where(((hour >= 6) & (hour < 9)) | ((hour >= 17) & (hour < 21)), 1.0, 0.5)
+    fuel = float(fuel_price) * np.where((month == 12) | (month <= 2), 1.25, 1.0)
+    return config4(scenarios, n=n, only=only,
+                   chp=dict(rated_power=rated_power, n=1.0, min_power=min_power, electric_heat_ratio=electric_heat_ratio,
+                            max_steam_ratio=max_steam_ratio, variable_om_cost=variable_om_cost, fixed_om=fixed_om,
+                            fuel_price=fuel, steam_load=steam, hotwater_load=hot))
 
 
 def reliability_min_soe(critical_load, hours=4.0, dt=1.0, cap=None):

@@ -169,6 +169,8 @@ class BatchSolver:
     _PATHS = {"default": 0, "generic": 1, "ell": 2, "band1": 3, "band3": 4, "interconnect": 5}
     # modes added after the six above, which tests/test_interconnect_path.py pins as a set: 6 the load-shift form
     _MORE_PATHS = {"load_shift": 6}
+    # ... and after that one, which tests/test_load_shift_path.py pins too: 7 the heat form
+    _CHP_PATHS = {"chp": 7}
 
     def set_kernel_path(self, path):
         """Kernel cascade: "default" (battery-banded -> ELL -> generic CSR), "ell" (ELL -> generic), "generic",
@@ -178,8 +180,12 @@ class BatchSolver:
         interconnection form: windows with POI limit rows, a curtailable-PV block or charge-from-PV rows count as
         band windows instead of ending on the generic kernel), or "load_shift" (the default cascade plus the band
         kernel's load-shift form: windows with a controllable load, ``builder.battery_group(ctrl_load=...)``, count
-        as band windows instead of ending on the ELL / generic kernels).  A bool selects "generic" (True) / "default" (False)."""
-        mode = (1 if path else 0) if isinstance(path, bool) else {**self._PATHS, **self._MORE_PATHS}[path]
+        as band windows instead of ending on the ELL / generic kernels), or "chp" (the default cascade plus the band
+        kernel's heat form: windows with a combined-heat-and-power unit, ``builder.battery_group(chp=...)``, count as
+        band windows instead of ending on the ELL / generic kernels or, from T = 586 steps on, on the one-window-at-a-
+        time path for windows above the on-chip size).  A bool selects "generic" (True) / "default" (False)."""
+        mode = (1 if path else 0) if isinstance(path, bool) else \
+            {**self._PATHS, **self._MORE_PATHS, **self._CHP_PATHS}[path]
         self._check(self._lib.dvh_set_kernel_path(self._h, mode), "dvh_set_kernel_path")
 
     def set_launch_order(self, order):

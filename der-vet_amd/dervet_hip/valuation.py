@@ -107,6 +107,8 @@ def bill_inputs(g, orig=None):
     inp = getattr(g, "inputs", None)
     if getattr(g, "ctrl_load", None) is not None:
         raise NotImplementedError("bill: windows with a controllable load are not valued")
+    if getattr(g, "chp", None) is not None:
+        raise NotImplementedError("bill: windows with a CHP are not valued")
     if inp is None:
         raise ValueError("bill: the window group carries no series (builder.battery_group records them in .inputs)")
     # (an EV group's inputs also carry what the device builder reads: ev_ch_max, ev_target, ev_code, ev_fixed_om)

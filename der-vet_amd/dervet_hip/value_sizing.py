@@ -288,6 +288,8 @@ class _Resident:
                 raise ValueError("every window position needs one row per case")
             if getattr(s, "ctrl_load", None) is not None:
                 raise NotImplementedError("economic sizing: windows with a controllable load are not supported")
+            if getattr(s, "chp", None) is not None:
+                raise NotImplementedError("economic sizing: windows with a CHP are not supported")
             if getattr(s, "ev", None) is not None:
                 raise NotImplementedError("economic sizing: windows with an EV are not supported")
             if s.ice is not None or s.emin is not None:

@@ -773,7 +773,16 @@ int dvh_value_master(dvh_handle* h, const dvh_value_master_args* args, void* str
  * by the load's T + D: per day the day-start row, the el recurrence and the day-end row; every DCM row may carry
  * pw_t), which mode 0 leaves to the ELL / generic kernels, are taken after the ICE pass by a 768-thread kernel of
  * their own and counted as band windows, as mode 5 does for its windows; dvh_options.kkt_predict is ignored by that
- * kernel and certify works through the after-pass.  One form is added at a time: mode 6 does not run mode 5's. */
+ * kernel and certify works through the after-pass.  One form is added at a time: mode 6 does not run mode 5's.
+ * 7 = as 0 plus the band kernel's heat form (opt-in): battery windows with one combined-heat-and-power unit
+ * (x = [ch, dis, ene, tau, elec, on, steam, hotwater], the battery's T + 1 equality rows followed by T heat rows
+ * (elec_t, steam_t, hotwater_t; right-hand side 0); among the >= rows, besides the DCM rows (which may carry elec_t),
+ * per step two generator rows (elec_t, on_t) and one ratio row (steam_t, hotwater_t), right-hand sides 0; 0 <= elec,
+ * 0 <= on <= a finite bound at no cost, steam and hotwater bounded below only), which mode 0 leaves to the ELL / generic
+ * kernels and, from n or m > 4096 on (T >= 586), to the grid-wide path one window at a time, are taken by a 768-thread
+ * kernel of their own (T <= 768) and counted as band windows; the windows up to 4096 after the ICE pass without a host
+ * wait, as modes 5 and 6, the larger ones behind their chunk's tiers with one status read-back per batch.
+ * dvh_options.kkt_predict is ignored by that kernel and certify works through the after-pass (up to 4096). */
 int dvh_set_kernel_path(dvh_handle* h, int mode);
 
 /* Launch order of the next solve (scheduling only: the results do not depend on it).  order: host array, a
